@@ -10,10 +10,18 @@ rank processes spawned before anything touches a GPU; with the nccl backend it
 exits non-zero when the node has fewer than N GPUs, GDSP_DIST_BACKEND=gloo
 rehearses N ranks on one GPU); the 65536 rows are split over the ranks
 (strong scaling; no data-path collective: the rows are
-independent). value = 2^28 samples / max-over-ranks wall time; at N > 1 a
-weak-scaling figure (65536 rows per rank) is added as "weak_scaling".
+independent). value = 2^28 samples / max-over-ranks wall time.
 
-The default run also times the other BASELINE configs and nests them under
+A plain run does what that figure needs and no more: set-up, warm-up, the
+--steps timed steps, the result line (roofline.achieved from the timed steps'
+own events; the profile figures quoted beside it are read from committed
+files). --dump-outputs DIR writes what the last timed step computed, for
+comparing two builds output for output. Everything below runs with --full
+only: oracle parity, cpu_baseline, at N > 1 a weak-scaling figure (65536 rows
+per rank, "weak_scaling"), the nested configs and the second timings some
+workloads carry.
+
+With --full the default run also times the other BASELINE configs and nests them under
 "configs": bluestein3000, chirpz3000, prime3001 and pfa3027 (configs[2]; the prime
 n = 3001 and the composite 3027 = 3 x 1009 through the production dispatch: Rader,
 and the prime-factor Rader kernel, each with its chirp-z plan timed beside it),
@@ -84,8 +92,8 @@ def parse():
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--workload", default="default",
                     choices=["default"] + WORKLOADS,
-                    help="default: the headline radix4096 line with the other BASELINE "
-                         "configs nested under 'configs'")
+                    help="default: the headline radix4096 line, with --full the other "
+                         "BASELINE configs nested under 'configs'")
     ap.add_argument("--batch", type=int, default=0,
                     help="rows in total, split over the ranks (0 = config default 65536)")
     ap.add_argument("--cpu-seconds", type=float, default=10.0,
@@ -93,6 +101,16 @@ def parse():
     ap.add_argument("--config-cpu-seconds", type=float, default=5.0,
                     help="target CPU seconds for each nested config's cpu_baseline")
     ap.add_argument("--check-rows", type=int, default=8, help="rows checked against the oracle")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beside the headline figure: the nested BASELINE configs, "
+                         "oracle parity, CPU baselines, weak scaling at N > 1, and the second "
+                         "timings some workloads carry (reference_m8192, chirpz, host_api, "
+                         "small_n, the fftreal1024 kernel alone)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the headline workload's last step "
+                         "computed to DIR/<name>.npy as float64 (complex values as a trailing "
+                         "axis of re, im); an output above 32 MiB is sampled along its first "
+                         "axis with a fixed seed")
     return ap.parse_args()
 
 
@@ -187,7 +205,8 @@ def setup(w: str, c: Ctx, weak: bool = False) -> dict:
             # bluestein.go:70 pads to 8192 (GDSP_ALGO_CHIRPZ_POW2 keeps it)
             algo = "Bluestein chirp-z (fused, M=6144=16*24*16; the reference pads to 8192)"
             kernel = "chirpz6k_kernel"
-        return dict(step=step, x=x, y=y, total_samples=total * n, rank_samples=(hi - lo) * n,
+        return dict(step=step, x=x, y=y, outputs=lambda: {"y": y},
+                    total_samples=total * n, rank_samples=(hi - lo) * n,
                     alg_bytes=32 * (hi - lo) * n, kernel=kernel, metric=HEADLINE_METRIC,
                     scaling="weak" if weak else "strong",
                     cfg={"workload": f"fft.FFT batched complex128 N={n} x {total} rows"
@@ -204,7 +223,8 @@ def setup(w: str, c: Ctx, weak: bool = False) -> dict:
         def step():
             D.fft2(x, y, work=work, stream=stream)
 
-        return dict(step=step, x=x, y=y, total_samples=rows * cols, rank_samples=rows * cols,
+        return dict(step=step, x=x, y=y, outputs=lambda: {"y": y},
+                    total_samples=rows * cols, rank_samples=rows * cols,
                     alg_bytes=2 * 2 * 16 * rows * cols, kernel="fft2 (all launches)",
                     metric="Gsamples/s, fft.FFT2 8192x8192 complex128", scaling="strong",
                     cfg={"workload": "fft.FFT2 complex128 8192x8192", "rows": rows,
@@ -220,7 +240,8 @@ def setup(w: str, c: Ctx, weak: bool = False) -> dict:
         def step():
             result["y"] = Dd.fft2_sharded(x, R, stream=stream)
 
-        return dict(step=step, total_samples=R * C, rank_samples=x.numel(),
+        return dict(step=step, outputs=lambda: {"y": result["y"]},
+                    total_samples=R * C, rank_samples=x.numel(),
                     alg_bytes=2 * 2 * 16 * x.numel(),
                     kernel="fft2_sharded (all launches and both all-to-alls)",
                     metric="Gsamples/s, fft.FFT2 8192x8192 complex128", scaling="strong",
@@ -238,7 +259,8 @@ def setup(w: str, c: Ctx, weak: bool = False) -> dict:
         def step():
             D.fft_batch(x, y, stream=stream)
 
-        return dict(step=step, x=x, y=y, total_samples=n * world, rank_samples=n,
+        return dict(step=step, x=x, y=y, outputs=lambda: {"y": y},
+                    total_samples=n * world, rank_samples=n,
                     alg_bytes=32 * n, kernel="four-step (colfft tile, row FFTs, transpose)",
                     metric="Gsamples/s, fft.FFT N=2^20 (BenchmarkFFT)", scaling="weak",
                     cfg={"workload": "fft.FFT of one N=2^20 complex128 vector (BenchmarkFFT, "
@@ -254,7 +276,8 @@ def setup(w: str, c: Ctx, weak: bool = False) -> dict:
         def step():
             D.fftn(x, y, stream=stream)
 
-        return dict(step=step, total_samples=x.numel() * world, rank_samples=x.numel(),
+        return dict(step=step, outputs=lambda: {"y": y},
+                    total_samples=x.numel() * world, rank_samples=x.numel(),
                     alg_bytes=3 * 2 * 16 * x.numel(),  # each axis: one read + one write
                     kernel="fftn (all launches: rows, then two column-tile axes)",
                     metric="Gsamples/s, fft.FFTN 512^3 complex128", scaling="weak",
@@ -276,7 +299,8 @@ def setup(w: str, c: Ctx, weak: bool = False) -> dict:
         def step():
             wav.device_floats(raw, count, 1, 16, out=y, stream=stream)
 
-        return dict(step=step, raw=raw, y=y, total_samples=count * world, rank_samples=count,
+        return dict(step=step, raw=raw, y=y, outputs=lambda: {"y": y},
+                    total_samples=count * world, rank_samples=count,
                     alg_bytes=10 * count,  # 2 B PCM16 in, 8 B float64 out
                     kernel="wav_decode_vec_kernel<16, f64>", dtype="pcm16 -> f64",
                     metric="Gsamples/s, wav.ReadFloats PCM16 2^30 samples", scaling="weak",
@@ -300,7 +324,8 @@ def setup(w: str, c: Ctx, weak: bool = False) -> dict:
         result["pxx"], _ = Dd.pwelch(x, 1.0, opts, sh, stream=stream)
 
     if w == "pwelch_default":
-        return dict(step=step, x=x, shard=sh, opts=opts, result=result, total_samples=total,
+        return dict(step=step, x=x, shard=sh, opts=opts, result=result,
+                    outputs=lambda: {"pxx": result["pxx"]}, total_samples=total,
                     rank_samples=total // world,
                     alg_bytes=8 * x.numel(), kernel="pwelch_wave_kernel<8, false, false>",
                     metric="Gsamples/s, spectral.Pwelch 2^30 samples, PwelchOptions{} defaults "
@@ -310,7 +335,8 @@ def setup(w: str, c: Ctx, weak: bool = False) -> dict:
                                      "default options: Hann NFFT 256, Noverlap 0, Pad 256",
                          "segments_total": sh.nsegs_total,
                          "parallelism": f"segments{world}+allreduce"})
-    return dict(step=step, x=x, shard=sh, opts=opts, result=result, total_samples=total,
+    return dict(step=step, x=x, shard=sh, opts=opts, result=result,
+                outputs=lambda: {"pxx": result["pxx"]}, total_samples=total,
                 rank_samples=total // world,
                 alg_bytes=8 * x.numel(), kernel="pwelch_row_kernel<12>",
                 metric="Gsamples/s, spectral.Pwelch 2^30 samples NFFT 4096 50% overlap",
@@ -371,6 +397,32 @@ def measure(wl: dict, c: Ctx) -> dict:
         elapsed = float(t.item())
     ev_ms = [s.elapsed_time(e) for s, e in zip(starts, ends)]
     return {"elapsed": elapsed, "avg_launch_s": sum(ev_ms) / len(ev_ms) / 1e3}
+
+
+DUMP_BYTES = 32 << 20  # --dump-outputs: the most one array takes on disk
+
+
+def dump_outputs(outputs: dict, c: Ctx) -> None:
+    """--dump-outputs: every array of the last timed step as DIR/<name>.npy
+    (<name>.rank<r>.npy at N > 1: each rank writes its shard's), float64,
+    complex128 as a trailing axis of (re, im). An array above DUMP_BYTES is
+    sampled along its first axis: the sorted indices that a generator seeded
+    with SEED draws without replacement, the same in every run."""
+    import numpy as np
+    os.makedirs(c.args.dump_outputs, exist_ok=True)
+    for name, a in outputs.items():
+        n0 = a.shape[0]
+        keep = DUMP_BYTES // (a.nbytes // n0)
+        if keep < n0:
+            idx = np.sort(np.random.default_rng(SEED).choice(n0, keep, replace=False))
+            a = a[c.torch.as_tensor(idx, device=a.device) if c.torch.is_tensor(a) else idx]
+        if c.torch.is_tensor(a):
+            a = a.cpu().numpy()
+        if np.iscomplexobj(a):
+            a = np.ascontiguousarray(a).view(np.float64).reshape(a.shape + (2,))
+        suffix = f".rank{c.rank}" if c.world > 1 else ""
+        np.save(os.path.join(c.args.dump_outputs, f"{name}{suffix}.npy"),
+                a.astype(np.float64, copy=False))
 
 
 def parity(w: str, wl: dict, c: Ctx):
@@ -486,14 +538,14 @@ def parity_pwelch(wl: dict, c: Ctx, np, oracle) -> dict:
             "nrel_host_api": e_host, "full_size": fs}
 
 
-def run_fftreal1024(c: Ctx) -> dict:
+def run_fftreal1024(c: Ctx, dump: bool = False) -> dict:
     """BASELINE configs[0]: fft.FFTReal of one N = 1024 float64 vector
     (fft/fft.go:25-27), called the way the reference is called: a host slice
     in, a fresh complex128 slice out, through the host-pointer C ABI
     (gdsp_fft_real: mapped pinned buffers, one launch, one synchronisation).
-    A step is one call; each timed step is the mean of 200 calls. The kernel's
-    own duration (HIP events, device-resident row) is the roofline figure."""
-    import numpy as np
+    A step is one call; each timed step is the mean of 200 calls. With --full
+    the kernel's own duration (HIP events, device-resident row) is timed as
+    the roofline figure, the result is checked and small_n is measured."""
     torch, D, args = c.torch, c.D, c.args
     n = 1024
     xd = torch.empty(n, dtype=torch.float64, device=c.dev)
@@ -510,6 +562,41 @@ def run_fftreal1024(c: Ctx) -> dict:
         y = fr(xh)
     elapsed = time.perf_counter() - t0
     per_call = elapsed / (args.steps * reps)
+    if dump and args.dump_outputs:
+        dump_outputs({"y": y}, c)
+    roofline = check = crossover = None
+    if args.full:
+        roofline, check, crossover = fftreal1024_full(c, xd, xh, y)
+    return {
+        "metric": "Gsamples/s (us per call), fft.FFTReal N=1024 on a host vector",
+        "value": round(n / per_call / 1e9, 6),
+        "unit": "Gsamples/s",
+        "small_n": crossover,
+        "ms_per_step": round(per_call * 1e3, 5),
+        "us_per_call": round(per_call * 1e6, 2),
+        "scaling": "weak",
+        "dtype": "f64 in, complex128 out",
+        "config": {"workload": "fft.FFTReal of one N=1024 float64 host vector per call "
+                               "(BASELINE configs[0]; host C ABI, PCIe-inclusive)",
+                   "n": n, "batch": 1, "calls_timed": args.steps * reps,
+                   "parallelism": f"replicas{c.world}"},
+        "roofline": roofline,
+        "fp64": None,
+        "cpu_baseline": None,
+        "parity": check,
+        "drop_in_policy": {
+            "gpu_min_n": 0, "source": "go/fft/fft_gpu.go",
+            "note": "every one-vector call of the drop-in goes to the C ABI (round 6: no reference "
+                    "FFT code in the gdspgpu build); small_n.first_n_gpu_faster is where a "
+                    "one-vector GPU call beats one host thread"},
+    }
+
+
+def fftreal1024_full(c: Ctx, xd, xh, y) -> tuple:
+    """The --full part of run_fftreal1024: (roofline, parity, small_n)."""
+    import numpy as np
+    torch, D, args = c.torch, c.D, c.args
+    n, reps = 1024, 200
     # the kernel alone: the same FFTReal on the device-resident float64 row
     # (gdsp_fft_real_batch_device: the LOAD_REAL kernel the host call runs)
     xr = xd.reshape(1, n)
@@ -536,36 +623,15 @@ def run_fftreal1024(c: Ctx) -> dict:
     crossover = None
     if c.rank == 0 and args.check_rows > 0:
         crossover = small_call_crossover(c, np, oracle)
-    return {
-        "metric": "Gsamples/s (us per call), fft.FFTReal N=1024 on a host vector",
-        "value": round(n / per_call / 1e9, 6),
-        "unit": "Gsamples/s",
-        "small_n": crossover,
-        "ms_per_step": round(per_call * 1e3, 5),
-        "us_per_call": round(per_call * 1e6, 2),
-        "scaling": "weak",
-        "dtype": "f64 in, complex128 out",
-        "config": {"workload": "fft.FFTReal of one N=1024 float64 host vector per call "
-                               "(BASELINE configs[0]; host C ABI, PCIe-inclusive)",
-                   "n": n, "batch": 1, "calls_timed": args.steps * reps,
-                   "parallelism": f"replicas{c.world}"},
-        "roofline": {"bound": "latency", "kernel": "fft_lds_kernel<10> (one float64 row, LOAD_REAL)",
-                     "achieved": round(alg / kern_s / 1e9, 3), "peak": HBM_PEAK_GBS,
-                     "unit": "GB/s", "frac": round(alg / kern_s / 1e9 / HBM_PEAK_GBS, 6),
-                     "frac_vs_copy": round(alg / kern_s / 1e9 / HBM_COPY_GBS, 6),
-                     "avg_launch_ms": round(kern_s * 1e3, 5), "alg_bytes_per_launch": alg,
-                     "traffic": None,
-                     "note": "one 24 KiB transform: launch-latency bound, not HBM bound; "
-                             "the call's cost is launch + synchronisation (us_per_call)"},
-        "fp64": None,
-        "cpu_baseline": None,
-        "parity": check,
-        "drop_in_policy": {
-            "gpu_min_n": 0, "source": "go/fft/fft_gpu.go",
-            "note": "every one-vector call of the drop-in goes to the C ABI (round 6: no reference "
-                    "FFT code in the gdspgpu build); small_n.first_n_gpu_faster is where a "
-                    "one-vector GPU call beats one host thread"},
-    }
+    roofline = {"bound": "latency", "kernel": "fft_lds_kernel<10> (one float64 row, LOAD_REAL)",
+                "achieved": round(alg / kern_s / 1e9, 3), "peak": HBM_PEAK_GBS,
+                "unit": "GB/s", "frac": round(alg / kern_s / 1e9 / HBM_PEAK_GBS, 6),
+                "frac_vs_copy": round(alg / kern_s / 1e9 / HBM_COPY_GBS, 6),
+                "avg_launch_ms": round(kern_s * 1e3, 5), "alg_bytes_per_launch": alg,
+                "traffic": None,
+                "note": "one 24 KiB transform: launch-latency bound, not HBM bound; "
+                        "the call's cost is launch + synchronisation (us_per_call)"}
+    return roofline, check, crossover
 
 
 def small_call_crossover(c: Ctx, np, oracle) -> dict:
@@ -594,13 +660,18 @@ def small_call_crossover(c: Ctx, np, oracle) -> dict:
     return {"by_n": rows, "first_n_gpu_faster": cross}
 
 
-def run(w: str, c: Ctx, weak: bool = False) -> dict:
-    """One workload: setup, timed steps, its bench-line fields."""
+def run(w: str, c: Ctx, weak: bool = False, dump: bool = False) -> dict:
+    """One workload: setup, timed steps, its bench-line fields. dump: this is
+    the run whose last step --dump-outputs writes. The oracle parity and the
+    second timings some workloads carry run only with --full."""
+    full = c.args.full
     if w == "fftreal1024":
-        return run_fftreal1024(c)
+        return run_fftreal1024(c, dump)
     wl = setup(w, c, weak=weak)
     m = measure(wl, c)
-    check = parity(w, wl, c)
+    if dump and c.args.dump_outputs:
+        dump_outputs(wl["outputs"](), c)
+    check = parity(w, wl, c) if full else None
     elapsed, avg_launch_s, args, world = m["elapsed"], m["avg_launch_s"], c.args, c.world
     value = wl["total_samples"] * args.steps / elapsed / 1e9
     achieved = wl["alg_bytes"] / avg_launch_s / 1e9
@@ -642,7 +713,7 @@ def run(w: str, c: Ctx, weak: bool = False) -> dict:
         "cpu_baseline": None,  # filled in by main() after every GPU measurement
         "parity": check,
     }
-    if w == "chirpz3000" and not weak and wl["kernel"] == "chirpz6k_kernel":
+    if full and w == "chirpz3000" and not weak and wl["kernel"] == "chirpz6k_kernel":
         # the same workload on the reference's convolution length M = 8192
         # (bluestein.go:70; GDSP_ALGO_CHIRPZ_POW2), timed the same way
         F = c.gdsp.fft
@@ -661,8 +732,8 @@ def run(w: str, c: Ctx, weak: bool = False) -> dict:
         del w8
         c.torch.cuda.empty_cache()
         return out
-    if (w, wl["kernel"]) in (("prime3001", "rader_fixed_kernel"),
-                             ("pfa3027", "rader_pfa_kernel")) and not weak:
+    if full and (w, wl["kernel"]) in (("prime3001", "rader_fixed_kernel"),
+                                      ("pfa3027", "rader_pfa_kernel")) and not weak:
         # the same prime on the chirp-z kernel it took before Rader
         # (GDSP_ALGO_NO_RADER: the fused chirp-z on M = 6144), timed the same way
         F = c.gdsp.fft
@@ -681,7 +752,7 @@ def run(w: str, c: Ctx, weak: bool = False) -> dict:
         del wc
         c.torch.cuda.empty_cache()
         return out
-    if c.rank == 0 and w == "fft_2p20":
+    if full and c.rank == 0 and w == "fft_2p20":
         # fft.FFT on a host vector, the way BenchmarkFFT calls it: H2D +
         # transform + D2H through the C ABI's pinned staging (PCIe-inclusive;
         # reported beside value, never as value)
@@ -896,7 +967,7 @@ def main():
     os.dup2(2, 1)
     c = Ctx(args)
     w = "radix4096" if args.workload == "default" else args.workload
-    head = run(w, c)
+    head = run(w, c, dump=True)
     line = {"metric": head["metric"], "value": head["value"], "unit": "Gsamples/s",
             "n_gpus": c.world, "steps": args.steps, "warmup": args.warmup,
             "ms_per_step": head["ms_per_step"], "higher_is_better": True,
@@ -907,11 +978,11 @@ def main():
     line.update({k: head[k] for k in ("config", "roofline", "fp64", "cpu_baseline", "parity")})
     if "host_api" in head:
         line["host_api"] = head["host_api"]
-    if c.world > 1 and w == "radix4096":
+    if args.full and c.world > 1 and w == "radix4096":
         # secondary: every rank with its own 65536 rows (weak scaling)
         weak = run(w, c, weak=True)
         line["weak_scaling"] = {k: weak[k] for k in ("value", "ms_per_step", "config")}
-    if args.workload == "default":
+    if args.full and args.workload == "default":
         line["configs"] = {}
         for cw in NESTED:
             r = run(cw, c)
@@ -919,7 +990,7 @@ def main():
             line["configs"][cw] = r
     # CPU baselines last, so that no GPU measurement follows seconds of an
     # idle GPU (rank 0 at N=1 only)
-    if c.rank == 0 and c.world == 1:
+    if args.full and c.rank == 0 and c.world == 1:
         if args.cpu_seconds > 0:
             line["cpu_baseline"] = cpu_baseline(w, args.cpu_seconds)
         for cw, r in line.get("configs", {}).items():

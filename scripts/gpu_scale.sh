@@ -18,7 +18,7 @@ timeout -k 10 900 python3 -u -m pytest tests/test_multi.py -m gpu -x -v --timeou
     --timeout-method thread > "$OUT/pytest_multi.log" 2>&1 || { echo "multi tests failed"; exit 1; }
 for N in 1 2 4 8; do
   [ "$N" -le "$NDEV" ] || break
-  timeout -k 10 900 python3 bench.py --gpus "$N" --steps "$STEPS" --warmup "$WARM" \
+  timeout -k 10 900 python3 bench.py --full --gpus "$N" --steps "$STEPS" --warmup "$WARM" \
       > "$OUT/bench_gpus$N.json" 2> "$OUT/bench_gpus$N.err" || { echo "N=$N failed"; exit 1; }
   cat "$OUT/bench_gpus$N.json"
 done

@@ -1,6 +1,7 @@
 """bench.py's multi-GPU launcher (`python bench.py --gpus N` with no
 torch.distributed.run around it): argument/environment logic and the
-spawn-and-wait of the rank processes, on the CPU."""
+spawn-and-wait of the rank processes, on the CPU; and what a plain run prints
+and --dump-outputs writes."""
 import importlib.util
 import json
 import os
@@ -189,3 +190,69 @@ def test_rank_device_check():
     assert b.rank_device_check(4, 0, "nccl", {}, 8) is not None
     # the gloo rehearsal shares one GPU
     assert b.rank_device_check(1, 1, "gloo", {"LOCAL_WORLD_SIZE": "2"}, 2) is None
+
+
+class _DumpCtx:
+    """What bench.dump_outputs reads of a run context."""
+
+    def __init__(self, out_dir, rank=0, world=1):
+        import argparse
+        import torch
+        self.torch, self.rank, self.world = torch, rank, world
+        self.args = argparse.Namespace(dump_outputs=str(out_dir))
+
+
+def test_dump_outputs_whole_and_sampled(tmp_path):
+    import numpy as np
+    b = _bench()
+    rng = np.random.default_rng(1)
+    small = rng.standard_normal((7, 5)) + 1j * rng.standard_normal((7, 5))
+    # 3 rows over the 32 MiB an array may take: a fixed sample of its rows
+    rows = b.DUMP_BYTES // (1024 * 8) + 3
+    big = np.arange(rows * 1024, dtype=np.float64).reshape(rows, 1024)
+    for d in ("a", "b"):
+        b.dump_outputs({"y": small, "pxx": big}, _DumpCtx(tmp_path / d))
+    y = np.load(tmp_path / "a" / "y.npy")
+    assert y.dtype == np.float64 and y.shape == (7, 5, 2)
+    assert np.array_equal(y[..., 0], small.real) and np.array_equal(y[..., 1], small.imag)
+    p = np.load(tmp_path / "a" / "pxx.npy")
+    assert p.dtype == np.float64 and p.shape == (rows - 3, 1024) and p.nbytes == b.DUMP_BYTES
+    first = p[:, 0] / 1024  # the row each sampled row came from
+    assert np.all(np.diff(first) > 0) and first[-1] < rows
+    assert np.array_equal(big[first.astype(int)], p)
+    assert np.array_equal(p, np.load(tmp_path / "b" / "pxx.npy"))  # the same sample every run
+    # at N > 1 each rank writes its own shard's
+    b.dump_outputs({"y": small}, _DumpCtx(tmp_path / "c", rank=1, world=2))
+    assert os.listdir(tmp_path / "c") == ["y.rank1.npy"]
+
+
+def _bench_line(*argv):
+    p = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--gpus", "1", *argv],
+                       capture_output=True, text=True, timeout=300)
+    assert p.returncode == 0, p.stderr[-2000:]
+    lines = [l for l in p.stdout.splitlines() if l.strip()]
+    assert len(lines) == 1, p.stdout
+    return json.loads(lines[0])
+
+
+@pytest.mark.gpu
+def test_plain_run_is_lean_and_dumps_its_last_step(tmp_path, oracle):
+    """A plain run: the headline line alone (no nested configs, parity or CPU
+    baseline: those are --full), exactly --steps timed steps, and the last
+    step's output written by --dump-outputs equal to the oracle's FFT of the
+    same seeded input."""
+    import numpy as np
+    batch, n = 48, 4096
+    line = _bench_line("--steps", "3", "--warmup", "1", "--batch", str(batch),
+                       "--dump-outputs", str(tmp_path))
+    assert line["steps"] == 3 and line["ms_per_step"] > 0 and line["higher_is_better"] is True
+    assert line["unit"] == "Gsamples/s" and line["dtype"] == "f64 (complex128)"
+    # ms_per_step is printed to 1e-4 ms and a step this small takes about 1e-2 ms
+    assert line["value"] == pytest.approx(batch * n / line["ms_per_step"] / 1e6, rel=0.02)
+    assert "configs" not in line and line["parity"] is None and line["cpu_baseline"] is None
+    y = np.load(tmp_path / "y.npy")
+    assert y.dtype == np.float64 and y.shape == (batch, n, 2)
+    x = oracle.fill_uniform(2 * batch * n, 0x5EED).view(np.complex128).reshape(batch, n)
+    ref = oracle.fft_rows(x)
+    got = y[..., 0] + 1j * y[..., 1]
+    assert max(np.linalg.norm(a - r) / np.linalg.norm(r) for a, r in zip(got, ref)) < 1e-9
