@@ -118,7 +118,7 @@ __device__ __forceinline__ void exchange_x1(cd (&v)[32], double *lx, int wr, int
 
 // bhatp[r * 256 + t] = bhat[K(t, r)] / (the 1/M of the IFFT is in bhat),
 // K = K0 + 32 K1 + 1024 K2 with K0 = lane bits 0-2 + 8 w, K1 = lane bits 3-5
-// + 8 (r >> 3), K2 = r & 7 (gdsp_api.hip builds it).
+// + 8 (r >> 3), K2 = r & 7 (dev_api.hip builds it).
 template <bool INV>
 __global__ __launch_bounds__(256, 2) void bluestein_shfl_kernel(
     const cd *__restrict__ in, cd *__restrict__ out, int64_t n, int64_t batch,
