@@ -48,6 +48,9 @@ SIGNATURES = {
     "gdsp_fft_real": (_I, [_P, _P, _I64]),
     "gdsp_ifft_real": (_I, [_P, _P, _I64]),
     "gdsp_convolve": (_I, [_P, _P, _P, _I64]),
+    "gdsp_convolve_batch": (_I, [_P, _P, _P, _I64, _I64, _I64]),
+    "gdsp_convolve_batch_device": (_I, [_P, _P, _P, _I64, _P, _I64, _P, _P]),
+    "gdsp_convolve_fused": (_I, [_P]),
     "gdsp_fft_batch": (_I, [_P, _P, _I64, _I64, _I]),
     "gdsp_fft_real_batch": (_I, [_P, _P, _I64, _I64]),
     "gdsp_fft2": (_I, [_P, _P, _I64, _I64, _I]),

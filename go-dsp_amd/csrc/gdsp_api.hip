@@ -66,7 +66,8 @@ bool lds_split_default() { return true; }
 std::atomic<unsigned> g_algo{GDSP_ALGO_DEFAULT};
 constexpr unsigned kAlgoAll = GDSP_ALGO_GENERIC_MIXED | GDSP_ALGO_NO_CHIRPZ_PARTS |
                               GDSP_ALGO_CHIRPZ_POW2 | GDSP_ALGO_CHIRPZ_UNFUSED |
-                              GDSP_ALGO_NO_RADER | GDSP_ALGO_NO_RACE;
+                              GDSP_ALGO_NO_RADER | GDSP_ALGO_NO_RACE |
+                              GDSP_ALGO_NO_FUSED_CONVOLVE;
 
 // Scratch device memory: a grow-only buffer per (device, stream, use-site
 // slot), allocated with hipMalloc. Reuse is ordered by the stream itself: a
@@ -80,7 +81,7 @@ constexpr unsigned kAlgoAll = GDSP_ALGO_GENERIC_MIXED | GDSP_ALGO_NO_CHIRPZ_PART
 enum Slot {
   SLOT_IN = 0, SLOT_OUT, SLOT_AUX, SLOT_AUX2, SLOT_GLOBAL, SLOT_GLOBAL_IN, SLOT_REAL,
   SLOT_BLU, SLOT_FFT2, SLOT_PW_PART, SLOT_PW_RED, SLOT_PW_BUF, SLOT_FS0, SLOT_FS1, SLOT_FS2,
-  SLOT_FS3, SLOT_FFTN, SLOT_MX0, SLOT_MX1, SLOT_PARTS, SLOT_COUNT
+  SLOT_FS3, SLOT_FFTN, SLOT_MX0, SLOT_MX1, SLOT_PARTS, SLOT_CONV, SLOT_COUNT
 };
 
 struct Workspace {
@@ -928,6 +929,90 @@ int gdsp_convolve(const double *x, const double *y, double *out, int64_t n) {
   HIPCHK(gdsp::launch_pointwise_mul(dx, dy, dz, n, s));
   STCHK(exec_plan(p, dz, dz, 1, true, gdsp::LOAD_COMPLEX, s));
   STCHK(copy_d2h(out, dz, bytes, s));
+  return GDSP_OK;
+}
+
+// Batched fft.Convolve. The fused kernel (convolve.hip) serves the one-kernel
+// powers of 2 from 2^kConvMinLog2 up; every other plan runs FFT, row
+// multiply, IFFT.
+static bool convolve_fused(const gdsp_plan *p) {
+  return p->kind == KIND_LDS && p->log2n >= gdsp::kConvMinLog2 &&
+         p->log2n <= gdsp::kMaxLdsLog2 && !(g_algo.load() & GDSP_ALGO_NO_FUSED_CONVOLVE);
+}
+
+// Argument checks shared by the host and device entries; *done: nothing to do
+static int convolve_check(int64_t n, int64_t batch, int64_t y_rows, const void *x, const void *y,
+                          const void *out, bool *done) {
+  *done = false;
+  if (n < 0 || batch < 0) return fail(GDSP_ERR_INVALID, "negative size");
+  if (y_rows != 1 && y_rows != batch)
+    return fail(GDSP_ERR_INVALID, "y_rows must be 1 or the batch");
+  if (batch == 0) {
+    *done = true;
+    return GDSP_OK;
+  }
+  if (n == 0) return fail(GDSP_ERR_EMPTY, "IFFT of an empty slice (index out of range)");
+  if (!x || !y || !out) return fail(GDSP_ERR_INVALID, "NULL pointer");
+  return GDSP_OK;
+}
+
+// work: y_rows * n, the spectrum of y
+static int convolve_rows(const gdsp_plan *p, const cd *x, const cd *y, int64_t y_rows, cd *out,
+                         int64_t batch, cd *work, hipStream_t s) {
+  const int64_t n = p->n, ystride = y_rows == 1 ? 0 : n;
+  STCHK(exec_plan(p, y, work, y_rows, false, gdsp::LOAD_COMPLEX, s));
+  if (convolve_fused(p)) {
+    HIPCHK(gdsp::launch_convolve_lds(p->log2n, x, out, batch, p->tw, work, ystride, s));
+    return GDSP_OK;
+  }
+  STCHK(exec_plan(p, x, out, batch, false, gdsp::LOAD_COMPLEX, s));
+  HIPCHK(gdsp::launch_pointwise_mul_rows(out, work, ystride, out, n, batch, s));
+  return exec_plan(p, out, out, batch, true, gdsp::LOAD_COMPLEX, s);
+}
+
+int gdsp_convolve_fused(const gdsp_plan *plan) { return plan && convolve_fused(plan) ? 1 : 0; }
+
+int gdsp_convolve_batch_device(const gdsp_plan *plan, const void *d_x, const void *d_y,
+                               int64_t y_rows, void *d_out, int64_t batch, void *d_work,
+                               void *stream) {
+  if (!plan) return fail(GDSP_ERR_INVALID, "NULL plan");
+  bool done = false;
+  STCHK(convolve_check(plan->n, batch, y_rows, d_x, d_y, d_out, &done));
+  if (done) return GDSP_OK;
+  hipStream_t s = (hipStream_t)stream;
+  DevBuf w;
+  cd *work = (cd *)d_work;
+  if (!work) {
+    STCHK(w.alloc((size_t)y_rows * (size_t)plan->n * sizeof(cd), s, SLOT_CONV));
+    work = (cd *)w.p;
+  }
+  return convolve_rows(plan, (const cd *)d_x, (const cd *)d_y, y_rows, (cd *)d_out, batch, work, s);
+}
+
+int gdsp_convolve_batch(const double *x, const double *y, double *out, int64_t n, int64_t batch,
+                        int64_t y_rows) {
+  bool done = false;
+  STCHK(convolve_check(n, batch, y_rows, x, y, out, &done));
+  if (done) return GDSP_OK;
+  gdsp_plan *p = nullptr;
+  STCHK(get_plan(n, &p));
+  hipStream_t s = thread_stream(p->device);
+  if (!s) return fail(GDSP_ERR_HIP, "stream creation failed");
+  const size_t xb = (size_t)batch * (size_t)n * sizeof(cd);
+  const size_t yb = (size_t)y_rows * (size_t)n * sizeof(cd);
+  DevBuf dx, dy;
+  STCHK(dx.alloc(xb, s, SLOT_IN));
+  STCHK(dy.alloc(2 * yb, s, SLOT_AUX));  // y, then its spectrum
+  cd *py = (cd *)dy.p;
+  STCHK(copy_h2d(dx.p, x, xb, s));
+  STCHK(copy_h2d(py, y, yb, s));
+  const int st = convolve_rows(p, (const cd *)dx.p, py, y_rows, (cd *)dx.p, batch,
+                               py + y_rows * n, s);
+  if (st != GDSP_OK) {
+    (void)hipStreamSynchronize(s);  // queued copies still read the staging halves
+    return st;
+  }
+  STCHK(copy_d2h(out, dx.p, xb, s));  // returns after the stream drained
   return GDSP_OK;
 }
 

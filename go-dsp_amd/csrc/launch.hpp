@@ -221,6 +221,17 @@ hipError_t launch_chirp_postmul(const cd *a, cd *out, int64_t n, int64_t m, int6
                                 const cd *chirp, bool inv, double scale, hipStream_t s);
 hipError_t launch_pointwise_mul(const cd *a, const cd *b, cd *out, int64_t count, hipStream_t s);
 hipError_t launch_scale(cd *a, int64_t count, double sc, hipStream_t s);
+// fused circular convolution of power-of-2 rows (convolve.hip): out row g =
+// IFFT_n(FFT_n(x row g) * FFT_n(y)) in one kernel, 2^kConvMinLog2 <= n <=
+// 2^kMaxLdsLog2. yspec = FFT_n(y) (the kernel applies the inverse's 1/n as it
+// stores); yspec_stride 0: one spectrum for every row, n: row g takes
+// yspec + g n. out may alias x, not yspec.
+constexpr int kConvMinLog2 = 8;
+hipError_t launch_convolve_lds(int log2n, const cd *x, cd *out, int64_t batch, const cd *tw,
+                               const cd *yspec, int64_t yspec_stride, hipStream_t s);
+// out[g n + k] = a[g n + k] * b[g b_stride + k] (b_stride 0 or n); out may alias a
+hipError_t launch_pointwise_mul_rows(const cd *a, const cd *b, int64_t b_stride, cd *out,
+                                     int64_t n, int64_t batch, hipStream_t s);
 // wav.ReadFloats conversion (wav.hip): audio_format 1 (bits 8 / 16) or 3
 hipError_t launch_wav_decode(const void *in, int64_t count, int audio_format, int bits,
                              void *out, bool f64, hipStream_t s);

@@ -89,6 +89,40 @@ def fft_batch(x, out=None, inverse: bool = False, stream=None, chirpz: bool = Fa
     return out
 
 
+def convolve_fused(n: int) -> bool:
+    """Whether convolve_batch runs rows of n on the fused one-kernel
+    convolution under the current algorithm flags (gdsp_convolve_fused)."""
+    return bool(lib().gdsp_convolve_fused(plan(n).handle))
+
+
+def convolve_batch(x, y, out=None, work=None, stream=None):
+    """fft.Convolve of every row of a (batch, n) complex128 CUDA tensor with y:
+    a 1-D tensor of n (one y for all rows) or a tensor of x's shape (row by
+    row). out may be x itself. work: scratch of y's size (complex128) for the
+    spectrum of y; with it the call does not allocate
+    (gdsp_convolve_batch_device)."""
+    torch = _torch()
+    assert x.is_cuda and x.dtype == torch.complex128 and x.dim() == 2 and x.is_contiguous()
+    assert y.is_cuda and y.dtype == torch.complex128 and y.is_contiguous()
+    assert y.device == x.device
+    if tuple(y.shape) != tuple(x.shape) and tuple(y.shape) != (x.shape[1],):
+        raise _lib.Panic(_lib.GDSP_ERR_UNEQUAL, "arrays not of equal size")
+    if out is None:
+        out = torch.empty_like(x)
+    assert out.shape == x.shape and out.dtype == x.dtype and out.is_contiguous()
+    if work is not None:
+        assert work.is_cuda and work.dtype == torch.complex128 and work.is_contiguous()
+        assert work.numel() >= y.numel()
+    y_rows = 1 if y.dim() == 1 else x.shape[0]
+    with torch.cuda.device(x.device):
+        p = plan(x.shape[1])
+        wp = _ptr(work) if work is not None else ctypes.c_void_p()
+        check(lib().gdsp_convolve_batch_device(p.handle, _ptr(x), _ptr(y), y_rows, _ptr(out),
+                                               x.shape[0], wp, _stream_ptr(stream, x.device)),
+              "convolve_batch_device")
+    return out
+
+
 def fft_real_batch(x, out=None, inverse: bool = False, stream=None, chirpz: bool = False):
     """fft.FFTReal / IFFTReal of the rows of a (batch, n) float64 CUDA tensor
     into a complex128 tensor (gdsp_fft_real_batch_device: the kernels read the

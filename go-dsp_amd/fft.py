@@ -69,6 +69,24 @@ def Convolve(x, y) -> np.ndarray:
     return out
 
 
+def ConvolveBatch(x, y) -> np.ndarray:
+    """Additive batched Convolve: every row of the (batch, n) array x
+    convolved with y — one y of n for all rows, or a (batch, n) array, row by
+    row. fft.Convolve (fft/fft.go:55-69) per row, with its panic for any
+    other shape of y."""
+    x = np.ascontiguousarray(np.asarray(x, dtype=np.complex128))
+    y = np.ascontiguousarray(np.asarray(y, dtype=np.complex128))
+    if x.ndim != 2:
+        raise ValueError("ConvolveBatch expects a 2-D (batch, n) array")
+    if y.shape != x.shape and y.shape != (x.shape[1],):
+        raise Panic(_lib.GDSP_ERR_UNEQUAL, "arrays not of equal size")
+    out = np.empty_like(x)
+    y_rows = 1 if y.ndim == 1 else x.shape[0]
+    check(lib().gdsp_convolve_batch(_p(x), _p(y), _p(out), x.shape[1], x.shape[0], y_rows),
+          "ConvolveBatch")
+    return out
+
+
 def FFTBatch(x, inverse: bool = False) -> np.ndarray:
     """Additive batched entry point: FFT (or IFFT) of every row
     of a (batch, n) complex array, in one GPU launch."""
@@ -207,6 +225,7 @@ ALGO_CHIRPZ_POW2 = 4
 ALGO_CHIRPZ_UNFUSED = 8
 ALGO_NO_RADER = 16
 ALGO_NO_RACE = 32
+ALGO_NO_FUSED_CONVOLVE = 64
 
 
 def SetAlgorithm(flags: int = ALGO_DEFAULT) -> None:

@@ -263,6 +263,19 @@ inline std::vector<complex> FFTBatch(const std::vector<complex> &x, size_t n, bo
   return r;
 }
 
+// Additive batched Convolve: the x.size() / n rows of x each convolved with
+// y, one y of n for all rows or one per row (y.size() == x.size()).
+inline std::vector<complex> ConvolveBatch(const std::vector<complex> &x,
+                                          const std::vector<complex> &y, size_t n) {
+  if (n == 0 || x.size() % n != 0 || (y.size() != n && y.size() != x.size()))
+    throw Panic(GDSP_ERR_UNEQUAL, "arrays not of equal size");
+  std::vector<complex> r(x.size());
+  const int64_t batch = (int64_t)(x.size() / n);
+  check(gdsp_convolve_batch(cp(x), cp(y), mp(r), (int64_t)n, batch, y.size() == n ? 1 : batch),
+        "ConvolveBatch");
+  return r;
+}
+
 // fft.FFTN / IFFTN — fft.go:157-192
 inline dsputils::Matrix fftn(const dsputils::Matrix &m, int inverse) {
   std::vector<int64_t> d(m.dims.begin(), m.dims.end());

@@ -244,6 +244,25 @@ func FFTBatch(x []complex128, n int, inverse bool) []complex128 {
 	return r
 }
 
+// ConvolveBatch: Convolve of each of the len(x)/n rows of n in x with y in one
+// call: one y of n for every row, or len(y) == len(x) for one y per row.
+// Powers of 2 from 256 to 16384 run one fused kernel (FFT, multiply, inverse
+// FFT without leaving the workgroup).
+func ConvolveBatch(x, y []complex128, n int) []complex128 {
+	if n <= 0 || len(x)%n != 0 || (len(y) != n && len(y) != len(x)) {
+		panic("arrays not of equal size")
+	}
+	r := make([]complex128, len(x))
+	batch := len(x) / n
+	yRows := batch
+	if len(y) == n {
+		yRows = 1
+	}
+	check(C.gdsp_convolve_batch(cplx(x), cplx(y), cplx(r), C.int64_t(n), C.int64_t(batch),
+		C.int64_t(yRows)))
+	return r
+}
+
 // FFTRealBatch: FFTReal of len(x)/n float64 rows of n in one call.
 func FFTRealBatch(x []float64, n int) []complex128 {
 	if n <= 0 || len(x)%n != 0 {

@@ -94,7 +94,12 @@ enum {
    * prime-factor Rader, each against the chirp-z plan it would replace; the
    * fused chirp-z on a smooth convolution length against the one on a power
    * of 2) and keeps the faster, take the cost model's candidate instead */
-  GDSP_ALGO_NO_RACE = 32
+  GDSP_ALGO_NO_RACE = 32,
+  /* gdsp_convolve_batch / gdsp_convolve_batch_device on the composed path
+   * (FFT, row multiply, IFFT: three kernels) also for the powers of 2 the
+   * fused one-kernel convolution serves. Read when the call is made, not
+   * when the plan is built. */
+  GDSP_ALGO_NO_FUSED_CONVOLVE = 64
 };
 /* Unknown bits → GDSP_ERR_INVALID (the selection is left unchanged). */
 int gdsp_set_algorithm(unsigned flags);
@@ -123,6 +128,16 @@ int gdsp_ifft_real(const double *x, double *out, int64_t n);
 /* fft.Convolve — fft/fft.go:55-69 (IFFT(FFT(x)·FFT(y))). The reference's
  * length check ("arrays not of equal size") is the caller's: both are n. */
 int gdsp_convolve(const double *x, const double *y, double *out, int64_t n);
+
+/* Additive batched fft.Convolve (no reference equivalent): rows of x (batch ×
+ * n complex128) each convolved with y: y_rows == 1 → one y (n complex128) for
+ * all rows, y_rows == batch → row by row (y is batch × n). fft.Convolve per
+ * row. n < 0, batch < 0, y_rows neither 1 nor batch, or a NULL pointer with
+ * batch > 0 → GDSP_ERR_INVALID; n == 0 with batch > 0 → GDSP_ERR_EMPTY (as
+ * gdsp_convolve); batch == 0 → GDSP_OK, nothing done. Runs on the current
+ * device. */
+int gdsp_convolve_batch(const double *x, const double *y, double *out,
+                        int64_t n, int64_t batch, int64_t y_rows);
 
 /* Additive batched entry point (no reference equivalent): the
  * same transform as fft.FFT / fft.IFFT applied to `batch` contiguous rows of n
@@ -309,6 +324,22 @@ int gdsp_fft_batch_device(const gdsp_plan *plan, const void *d_in, void *d_out,
  * semantics (an empty plan is then GDSP_ERR_EMPTY, like IFFT). */
 int gdsp_fft_real_batch_device(const gdsp_plan *plan, const double *d_in, void *d_out,
                                int64_t batch, int inverse, void *stream);
+
+/* gdsp_convolve_batch on device buffers, rows of plan's length n: d_x and
+ * d_out hold batch*n complex128 (d_out may alias d_x), d_y y_rows*n (y_rows 1
+ * or batch). d_work: scratch of y_rows*n complex128 for the spectrum of y,
+ * distinct from d_out (may be NULL: the library allocates); with d_work given
+ * the call neither allocates nor synchronises where the plan's transform
+ * does not. Power-of-2 n from 256 to 16384 run one fused kernel per call after
+ * the spectrum of y (load, FFT, times FFT(y)/n, second FFT, store: one read
+ * and one write of the rows); every other length FFT, row multiply, IFFT.
+ * Status codes as gdsp_convolve_batch, n == 0 included; a NULL plan →
+ * GDSP_ERR_INVALID. */
+int gdsp_convolve_batch_device(const gdsp_plan *plan, const void *d_x, const void *d_y,
+                               int64_t y_rows, void *d_out, int64_t batch,
+                               void *d_work, void *stream);
+/* 1: the fused kernel serves this plan under the current flags; 0: composed */
+int gdsp_convolve_fused(const gdsp_plan *plan);
 
 /* FFT2/IFFT2 on a device rows×cols complex128 matrix. d_work: scratch of
  * rows*cols complex128 (may be NULL: the library allocates stream-ordered). */
