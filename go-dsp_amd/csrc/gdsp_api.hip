@@ -67,7 +67,7 @@ std::atomic<unsigned> g_algo{GDSP_ALGO_DEFAULT};
 constexpr unsigned kAlgoAll = GDSP_ALGO_GENERIC_MIXED | GDSP_ALGO_NO_CHIRPZ_PARTS |
                               GDSP_ALGO_CHIRPZ_POW2 | GDSP_ALGO_CHIRPZ_UNFUSED |
                               GDSP_ALGO_NO_RADER | GDSP_ALGO_NO_RACE |
-                              GDSP_ALGO_NO_FUSED_CONVOLVE;
+                              GDSP_ALGO_NO_FUSED_CONVOLVE | GDSP_ALGO_NO_FUSED_PWELCH_BATCH;
 
 // Scratch device memory: a grow-only buffer per (device, stream, use-site
 // slot), allocated with hipMalloc. Reuse is ordered by the stream itself: a
@@ -1533,6 +1533,175 @@ int gdsp_pwelch(const double *x, int64_t n, double fs, int64_t nfft, int64_t pad
   return GDSP_OK;
 }
 
+// ---- batched Pwelch: the channels of a planar batch in one call ---------------
+// The batched kernel (pwelch_batch.hip) serves the lengths of the wave
+// kernels; every other length and stride, and any shape under
+// GDSP_ALGO_NO_FUSED_PWELCH_BATCH, loops over the channels with
+// gdsp_pwelch_accumulate_device. Host arithmetic only.
+static bool pwelch_batch_fused(int64_t flen, int64_t stride) {
+  return flen > 0 && gdsp_api::is_pow2(flen) &&
+         gdsp::pwelch_batch_applies(gdsp_api::ilog2(flen)) && stride <= ((int64_t)1 << 22) &&
+         !(g_algo.load() & GDSP_ALGO_NO_FUSED_PWELCH_BATCH);
+}
+
+int gdsp_pwelch_batch_fused(int64_t channels, int64_t n, int64_t nfft, int64_t pad,
+                            int64_t noverlap) {
+  if (channels < 0 || n < 0) return 0;
+  if (nfft == 0) nfft = 256;
+  if (pad == 0) pad = nfft;
+  if (nfft < 0 || pad < 0) return 0;
+  return pwelch_batch_fused(pad > nfft ? pad : nfft, nfft - noverlap) ? 1 : 0;
+}
+
+int gdsp_pwelch_batch_accumulate_device(const double *d_x, int64_t channels, int64_t n,
+                                        int64_t ldx, int64_t nfft, int64_t pad, int64_t noverlap,
+                                        int64_t seg_begin, int64_t seg_end,
+                                        const double *d_win_seg, double *d_acc, void *stream) {
+  if (nfft <= 0 || pad <= 0 || seg_begin < 0 || seg_end < seg_begin)
+    return fail(GDSP_ERR_INVALID, "bad Pwelch geometry");
+  if (channels < 0 || n < 0 || (channels > 1 && ldx < n))
+    return fail(GDSP_ERR_INVALID, "bad batch geometry");
+  if (channels == 0 || seg_end == seg_begin) return GDSP_OK;
+  if (!d_x || !d_win_seg || !d_acc) return fail(GDSP_ERR_INVALID, "NULL pointer");
+  const int64_t stride = nfft - noverlap;
+  if ((seg_end - 1) * stride + nfft > n && seg_end > 1)
+    return fail(GDSP_ERR_INVALID, "segments exceed the signal");
+  const int64_t flen = pad > nfft ? pad : nfft;
+  hipStream_t s = (hipStream_t)stream;
+  gdsp_plan *p = nullptr;
+  if (pwelch_batch_fused(flen, stride)) STCHK(get_plan(flen, &p));
+  if (!p || p->kind != KIND_LDS) {
+    for (int64_t c = 0; c < channels; ++c)
+      STCHK(gdsp_pwelch_accumulate_device(d_x + c * ldx, n, nfft, pad, noverlap, seg_begin,
+                                          seg_end, d_win_seg, d_acc + c * flen, stream));
+    return GDSP_OK;
+  }
+  const bool half = 2 * noverlap == nfft && flen == nfft;
+  int64_t wpc = 0, gpw = 0, rows = 0;
+  gdsp::pwelch_batch_geometry(p->log2n, half, channels, seg_end - seg_begin, &wpc, &gpw, &rows);
+  // channels per launch: the partials within the materialised path's 512 MiB
+  int64_t cpl = ((int64_t)1 << 26) / (rows * flen);
+  if (cpl < 1) cpl = 1;
+  if (cpl > channels) cpl = channels;
+  DevBuf part, red;
+  STCHK(part.alloc((size_t)cpl * (size_t)rows * (size_t)flen * sizeof(double), s, SLOT_PW_PART));
+  STCHK(red.alloc((size_t)gdsp::reduce_batch_scratch_doubles(cpl, rows, flen) * sizeof(double), s,
+                  SLOT_PW_RED));
+  for (int64_t c0 = 0; c0 < channels; c0 += cpl) {
+    const int64_t nc = channels - c0 < cpl ? channels - c0 : cpl;
+    HIPCHK(gdsp::launch_pwelch_batch(p->log2n, half, d_x + c0 * ldx, ldx, nc, wpc, nfft, stride,
+                                     seg_begin, seg_end, gpw, d_win_seg, p->tw, (double *)part.p,
+                                     s));
+    HIPCHK(gdsp::launch_reduce_batch((const double *)part.p, nc, rows, flen, d_acc + c0 * flen,
+                                     (double *)red.p, s));
+  }
+  return GDSP_OK;
+}
+
+int gdsp_pwelch_batch_finalize_device(const double *d_acc, int64_t channels, int64_t flen,
+                                      int64_t nsegs, int64_t nfft, int64_t pad,
+                                      const double *win_nfft, double fs, int scale_off,
+                                      double *d_pxx, double *freqs, void *stream) {
+  if (channels < 0 || flen <= 0 || nfft <= 0 || pad <= 0 || nsegs < 0)
+    return fail(GDSP_ERR_INVALID, "bad argument");
+  if (channels > 0 && (!d_acc || !d_pxx)) return fail(GDSP_ERR_INVALID, "NULL pointer");
+  const int64_t lp = pad / 2 + 1;
+  if (lp > flen) return fail(GDSP_ERR_INVALID, "accumulators shorter than Pad / 2 + 1");
+  std::vector<double> hw;
+  if (!win_nfft) {
+    hw.resize((size_t)nfft);
+    hann_table(nfft, hw.data());
+    win_nfft = hw.data();
+  }
+  double norm = 0;  // as gdsp_pwelch_finalize
+  for (int64_t i = 0; i < nfft; ++i) norm += win_nfft[i] * win_nfft[i];
+  if (!scale_off) norm *= fs;
+  if (freqs) {
+    const double coef = fs / (double)pad;
+    for (int64_t j = 0; j < lp; ++j) freqs[j] = (double)j * coef;
+  }
+  if (channels == 0) return GDSP_OK;
+  HIPCHK(gdsp::launch_pwelch_finalize(d_acc, channels, flen, lp, nsegs, norm, d_pxx,
+                                      (hipStream_t)stream));
+  return GDSP_OK;
+}
+
+int gdsp_pwelch_batch(const double *x, int64_t channels, int64_t n, int64_t ldx, double fs,
+                      int64_t nfft, int64_t pad, int64_t noverlap, const double *win_seg,
+                      const double *win_nfft, int scale_off, double *pxx, double *freqs,
+                      int64_t *lp_out) {
+  if (!lp_out) return fail(GDSP_ERR_INVALID, "NULL pointer");
+  *lp_out = 0;
+  if (channels < 0 || n < 0) return fail(GDSP_ERR_INVALID, "negative size");
+  if (n == 0) return GDSP_OK;
+  if (nfft == 0) nfft = 256;
+  if (pad == 0) pad = nfft;
+  if (nfft < 0 || pad < 0) return fail(GDSP_ERR_INVALID, "negative NFFT/Pad");
+  if (channels > 1 && ldx < n) return fail(GDSP_ERR_INVALID, "ldx below the channel length");
+  const int64_t lx = n < nfft ? nfft : n;  // dsputils.ZeroPadF(x, nfft) per channel
+  int64_t nsegs = 0;
+  STCHK(segment_count(lx, nfft, noverlap, &nsegs));
+  if (!freqs || (channels > 0 && (!x || !pxx))) return fail(GDSP_ERR_INVALID, "NULL pointer");
+  const int64_t flen = pad > nfft ? pad : nfft;
+  const int64_t lp = pad / 2 + 1;
+  std::vector<double> hseg, hnfft;
+  if (!win_seg) {
+    hseg.resize((size_t)flen);
+    hann_table(flen, hseg.data());
+    win_seg = hseg.data();
+  }
+  if (!win_nfft) {
+    hnfft.resize((size_t)nfft);
+    hann_table(nfft, hnfft.data());
+    win_nfft = hnfft.data();
+  }
+  if (channels == 0) {
+    const double coef = fs / (double)pad;
+    for (int64_t j = 0; j < lp; ++j) freqs[j] = (double)j * coef;
+    *lp_out = lp;
+    return GDSP_OK;
+  }
+  std::vector<double> acc((size_t)channels * (size_t)flen, 0.0);
+  if (nsegs > 0) {
+    int dev = 0;
+    STCHK(current_device(&dev));
+    hipStream_t s = thread_stream(dev);
+    if (!s) return fail(GDSP_ERR_HIP, "stream creation failed");
+    const size_t abytes = acc.size() * sizeof(double);
+    DevBuf dx, dw, dacc;
+    STCHK(dx.alloc((size_t)channels * (size_t)lx * sizeof(double), s, SLOT_IN));
+    STCHK(dw.alloc((size_t)flen * sizeof(double), s, SLOT_AUX));
+    STCHK(dacc.alloc(abytes, s, SLOT_AUX2));
+    double *px = (double *)dx.p;
+    int st = GDSP_OK;
+    if (lx > n && hipMemsetAsync(px, 0, (size_t)channels * (size_t)lx * sizeof(double), s) !=
+                      hipSuccess)
+      st = fail(GDSP_ERR_HIP, "hipMemsetAsync failed");
+    if (st == GDSP_OK && lx == n && (ldx == n || channels == 1)) {
+      st = copy_h2d(px, x, (size_t)channels * (size_t)n * sizeof(double), s);
+    } else {
+      for (int64_t c = 0; c < channels && st == GDSP_OK; ++c)
+        st = copy_h2d(px + c * lx, x + c * ldx, (size_t)n * sizeof(double), s);
+    }
+    if (st == GDSP_OK) st = copy_h2d(dw.p, win_seg, (size_t)flen * sizeof(double), s);
+    if (st == GDSP_OK && hipMemsetAsync(dacc.p, 0, abytes, s) != hipSuccess)
+      st = fail(GDSP_ERR_HIP, "hipMemsetAsync failed");
+    if (st == GDSP_OK)
+      st = gdsp_pwelch_batch_accumulate_device(px, channels, lx, lx, nfft, pad, noverlap, 0, nsegs,
+                                               (const double *)dw.p, (double *)dacc.p, s);
+    if (st != GDSP_OK) {
+      (void)hipStreamSynchronize(s);  // queued copies still read the staging halves
+      return st;
+    }
+    STCHK(copy_d2h(acc.data(), dacc.p, abytes, s));
+  }
+  for (int64_t c = 0; c < channels; ++c)
+    STCHK(gdsp_pwelch_finalize(acc.data() + c * flen, flen, nsegs, nfft, pad, win_nfft, fs,
+                               scale_off, pxx + c * lp, freqs));
+  *lp_out = lp;
+  return GDSP_OK;
+}
+
 static bool wav_format_ok(int audio_format, int bits) {
   return (audio_format == 1 && (bits == 8 || bits == 16)) || audio_format == 3;
 }
@@ -1552,6 +1721,23 @@ int gdsp_wav_read_floats_device(const void *d_in, int64_t count, int audio_forma
   STCHK(current_device(&dev));
   HIPCHK(gdsp::launch_wav_decode(d_in, count, audio_format, bits_per_sample, d_out, out_f64 != 0,
                                  (hipStream_t)stream));
+  return GDSP_OK;
+}
+
+int gdsp_wav_read_floats_planar_device(const void *d_in, int64_t frames, int64_t channels,
+                                       int audio_format, int bits_per_sample, double *d_out,
+                                       int64_t ld_out, void *stream) {
+  if (frames < 0 || channels < 0 || channels > 65535 || (channels > 1 && ld_out < frames) ||
+      (frames && channels && (!d_in || !d_out)))
+    return fail(GDSP_ERR_INVALID, "bad argument");
+  if (!wav_format_ok(audio_format, bits_per_sample))
+    return fail(GDSP_ERR_UNSUPPORTED, audio_format == 1 ? "wav: unknown bits per sample"
+                                                        : "wav: unknown audio format");
+  if (frames == 0 || channels == 0) return GDSP_OK;
+  int dev = 0;
+  STCHK(current_device(&dev));
+  HIPCHK(gdsp::launch_wav_decode_planar(d_in, frames, (int)channels, audio_format,
+                                        bits_per_sample, d_out, ld_out, (hipStream_t)stream));
   return GDSP_OK;
 }
 

@@ -65,6 +65,24 @@ void pwelch_wave_geometry(int log2f, bool half, int64_t nsegs, int64_t *gpw, int
 hipError_t launch_pwelch_wave(int log2f, bool half, const double *x, int64_t nfft, int64_t stride,
                               int64_t seg_begin, int64_t seg_end, int64_t gpw, int64_t nblk,
                               const double *win, const cd *tw, double *partial, hipStream_t s);
+// the same kernel family over the channels of a planar batch (pwelch_batch.hip),
+// channel c at x + c ldx: workers per channel (wpc), pair groups per worker
+// and partial rows per channel for the whole job; the launch over `channels`
+// channels into partial[channel][rows][F]; the fixed-order reduce of every
+// channel's rows into acc + c F (scratch: reduce_batch_scratch_doubles); and
+// gdsp_pwelch_finalize's arithmetic per channel into pxx[channel][lp]
+bool pwelch_batch_applies(int log2f);
+void pwelch_batch_geometry(int log2f, bool half, int64_t channels, int64_t nsegs, int64_t *wpc,
+                           int64_t *gpw, int64_t *rows);
+hipError_t launch_pwelch_batch(int log2f, bool half, const double *x, int64_t ldx,
+                               int64_t channels, int64_t wpc, int64_t nfft, int64_t stride,
+                               int64_t seg_begin, int64_t seg_end, int64_t gpw, const double *win,
+                               const cd *tw, double *partial, hipStream_t s);
+int64_t reduce_batch_scratch_doubles(int64_t channels, int64_t rows, int64_t F);
+hipError_t launch_reduce_batch(const double *partial, int64_t channels, int64_t rows, int64_t F,
+                               double *acc, double *scratch, hipStream_t s);
+hipError_t launch_pwelch_finalize(const double *acc, int64_t channels, int64_t flen, int64_t lp,
+                                  int64_t nsegs, double norm, double *pxx, hipStream_t s);
 // fused Pwelch on a compiled specialisation (d = the plan's specialisation
 // descriptor, d.n = max(pad, nfft)); workers per block, 0 if d is none or
 // its kernel cannot stage a pair of span = stride + nfft samples
@@ -235,6 +253,10 @@ hipError_t launch_pointwise_mul_rows(const cd *a, const cd *b, int64_t b_stride,
 // wav.ReadFloats conversion (wav.hip): audio_format 1 (bits 8 / 16) or 3
 hipError_t launch_wav_decode(const void *in, int64_t count, int audio_format, int bits,
                              void *out, bool f64, hipStream_t s);
+// interleaved frames into planar float64 rows: out[c ld + i] = sample c of frame i
+hipError_t launch_wav_decode_planar(const void *in, int64_t frames, int channels,
+                                    int audio_format, int bits, double *out, int64_t ld,
+                                    hipStream_t s);
 hipError_t launch_fill_uniform(double *out, int64_t count, uint64_t seed, uint64_t offset,
                                hipStream_t s);
 

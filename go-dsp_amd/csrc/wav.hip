@@ -123,6 +123,49 @@ static hipError_t launch_fmt(const unsigned char *b, int64_t count, void *out, b
   return hipGetLastError();
 }
 
+// Interleaved frames into planar float64 rows, out[c ld + i] = the widened
+// sample c of frame i: a thread per frame walks its frame's channels, so the
+// stores of a wave are 512 contiguous bytes of one row at a time and the
+// frame bytes a wave reads (64 * channels samples, contiguous) are each used
+// once out of L2. Byte loads: a data chunk sits at any alignment.
+template <int FMT>
+__global__ __launch_bounds__(256) void wav_decode_planar_kernel(
+    const unsigned char *__restrict__ in, int64_t frames, int channels, double *__restrict__ out,
+    int64_t ld) {
+  constexpr int B = FMT / 8;
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < frames;
+       i += (int64_t)gridDim.x * blockDim.x) {
+    const unsigned char *p = in + i * channels * B;
+    for (int c = 0; c < channels; ++c, p += B) {
+      uint32_t u = p[0];
+      if constexpr (B >= 2) u |= (uint32_t)p[1] << 8;
+      if constexpr (B == 4) u |= ((uint32_t)p[2] << 16) | ((uint32_t)p[3] << 24);
+      out[c * ld + i] = (double)wav_sample<FMT>(u);
+    }
+  }
+}
+
+hipError_t launch_wav_decode_planar(const void *in, int64_t frames, int channels,
+                                    int audio_format, int bits, double *out, int64_t ld,
+                                    hipStream_t s) {
+  const unsigned char *b = (const unsigned char *)in;
+  if (frames <= 0 || channels <= 0) return hipSuccess;
+  int64_t nb = (frames + 255) / 256;
+  if (nb > 65536) nb = 65536;
+  const dim3 grid((unsigned)nb), block(256);
+  if (audio_format == 1 && bits == 8)
+    hipLaunchKernelGGL(wav_decode_planar_kernel<8>, grid, block, 0, s, b, frames, channels, out, ld);
+  else if (audio_format == 1 && bits == 16)
+    hipLaunchKernelGGL(wav_decode_planar_kernel<16>, grid, block, 0, s, b, frames, channels, out,
+                       ld);
+  else if (audio_format == 3)
+    hipLaunchKernelGGL(wav_decode_planar_kernel<32>, grid, block, 0, s, b, frames, channels, out,
+                       ld);
+  else
+    return hipErrorInvalidValue;
+  return hipGetLastError();
+}
+
 hipError_t launch_wav_decode(const void *in, int64_t count, int audio_format, int bits,
                              void *out, bool f64, hipStream_t s) {
   const unsigned char *b = (const unsigned char *)in;

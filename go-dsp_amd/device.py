@@ -211,3 +211,74 @@ def pwelch_accumulate(x, nfft: int, pad: int, noverlap: int, seg_begin: int, seg
             _ptr(x), x.numel(), nfft, pad, noverlap, seg_begin, seg_end, _ptr(win_seg), _ptr(acc),
             _stream_ptr(stream, x.device)), "pwelch_accumulate")
     return acc
+
+
+def pwelch_batch_accumulate(x, nfft: int, pad: int, noverlap: int, seg_begin: int, seg_end: int,
+                            win_seg, acc, stream=None):
+    """pwelch_accumulate over the rows of a 2-D float64 CUDA tensor (channels,
+    n) with unit inner stride and any row stride: adds the sums of segments
+    [seg_begin, seg_end) of row c into acc[c] (acc: (channels, max(pad, nfft))
+    float64, contiguous). One fused kernel over all rows where
+    spectral.pwelch_batch_fused says so (gdsp_pwelch_batch_accumulate_device)."""
+    torch = _torch()
+    assert x.is_cuda and x.dtype == torch.float64 and x.dim() == 2
+    channels, n = x.shape
+    assert n == 0 or x.stride(1) == 1, "rows must have unit inner stride"
+    ldx = x.stride(0) if channels > 1 else n
+    assert ldx >= n, "rows overlap"
+    flen = max(pad, nfft)
+    assert acc.is_cuda and acc.dtype == torch.float64 and acc.is_contiguous()
+    assert acc.numel() >= channels * flen
+    assert win_seg.is_cuda and win_seg.dtype == torch.float64 and win_seg.numel() >= flen
+    with torch.cuda.device(x.device):
+        check(lib().gdsp_pwelch_batch_accumulate_device(
+            _ptr(x), channels, n, ldx, nfft, pad, noverlap, seg_begin, seg_end, _ptr(win_seg),
+            _ptr(acc), _stream_ptr(stream, x.device)), "pwelch_batch_accumulate")
+    return acc
+
+
+def pwelch_batch(x, Fs: float, o, out=None, acc=None, stream=None):
+    """spectral.Pwelch of every row of a (channels, n) float64 CUDA tensor
+    (unit inner stride, any row stride), device-resident end to end: returns
+    the (channels, pad // 2 + 1) PSD tensor on x's device and freqs (numpy).
+    Row c equals spectral.Pwelch(x[c], Fs, o). out / acc: caller's result and
+    accumulator tensors ((channels, lp) and (channels, max(pad, nfft))
+    float64, contiguous); acc is overwritten."""
+    import contextlib
+
+    import numpy as np
+
+    from . import distributed, spectral
+    torch = _torch()
+    assert x.is_cuda and x.dtype == torch.float64 and x.dim() == 2
+    channels, n = x.shape
+    dev = x.device
+    if n == 0:  # pwelch.go:75-77
+        return torch.zeros((channels, 0), dtype=torch.float64, device=dev), np.zeros(0)
+    nfft, pad, noverlap, wf, scaling = spectral.resolve_options(o)
+    flen, lp = max(pad, nfft), pad // 2 + 1
+    ctx = torch.cuda.stream(stream) if stream is not None else contextlib.nullcontext()
+    with torch.cuda.device(dev), ctx:
+        if n < nfft:  # pwelch.go:97-99: zero-padded to nfft
+            x = torch.nn.functional.pad(x, (0, nfft - n))
+        nsegs = spectral.segment_count(x.shape[1], nfft, noverlap)
+        win_seg = distributed._device_window(wf, flen, dev, torch)
+        if acc is None:
+            acc = torch.zeros((channels, flen), dtype=torch.float64, device=dev)
+        else:
+            assert acc.is_cuda and acc.dtype == torch.float64 and acc.is_contiguous()
+            assert acc.numel() >= channels * flen
+            acc.view(-1)[:channels * flen].zero_()
+        if out is None:
+            out = torch.empty((channels, lp), dtype=torch.float64, device=dev)
+        assert out.is_cuda and out.dtype == torch.float64 and out.is_contiguous()
+        assert out.numel() >= channels * lp
+        if nsegs > 0:
+            pwelch_batch_accumulate(x, nfft, pad, noverlap, 0, nsegs, win_seg, acc, stream)
+        win_nfft = np.ascontiguousarray(wf(nfft), dtype=np.float64)
+        freqs = np.empty(lp, np.float64)
+        check(lib().gdsp_pwelch_batch_finalize_device(
+            _ptr(acc), channels, flen, nsegs, nfft, pad, win_nfft.ctypes.data_as(_lib._P),
+            float(Fs), int(not scaling), _ptr(out), freqs.ctypes.data_as(_lib._P),
+            _stream_ptr(stream, dev)), "pwelch_batch_finalize")
+    return out, freqs

@@ -7,6 +7,7 @@
 // GPU; a missing device surfaces as gdsp::Error (GDSP_ERR_NO_DEVICE).
 #pragma once
 
+#include <algorithm>
 #include <cmath>
 #include <cstdio>
 #include <istream>
@@ -424,6 +425,36 @@ inline std::pair<std::vector<double>, std::vector<double>> Pwelch(const std::vec
   pxx.resize((size_t)lpo);
   freqs.resize((size_t)lpo);
   return {pxx, freqs};
+}
+
+// Pwelch of every row of x (equal lengths: the channels of a recording) in
+// one call (gdsp_pwelch_batch): Pxx row c is Pwelch(x[c], Fs, o). Rows of
+// different lengths throw Panic ("ragged input array").
+inline std::pair<std::vector<std::vector<double>>, std::vector<double>> PwelchBatch(
+    const std::vector<std::vector<double>> &x, double Fs, const PwelchOptions *o) {
+  const size_t channels = x.size(), n = channels ? x[0].size() : 0;
+  for (const auto &r : x)
+    if (r.size() != n) throw Panic(GDSP_ERR_RAGGED, gdsp_status_string(GDSP_ERR_RAGGED));
+  if (n == 0) return {std::vector<std::vector<double>>(channels), {}};
+  if (!o) throw Panic(GDSP_ERR_INVALID, "invalid memory address or nil pointer dereference");
+  const int nfft = o->NFFT ? o->NFFT : 256;
+  const int pad = o->Pad ? o->Pad : nfft;
+  const window::Func wf = o->Window ? o->Window : window::Func(window::Hann);
+  const int flen = pad > nfft ? pad : nfft;
+  const auto wseg = wf(flen), wnfft = wf(nfft);
+  const size_t lp = (size_t)(pad / 2 + 1);
+  std::vector<double> flat(channels * n), pxx(channels * lp), freqs(lp);
+  for (size_t c = 0; c < channels; ++c) std::copy(x[c].begin(), x[c].end(), flat.begin() + c * n);
+  int64_t lpo = 0;
+  check(gdsp_pwelch_batch(flat.data(), (int64_t)channels, (int64_t)n, (int64_t)n, Fs, nfft, pad,
+                          o->Noverlap, wseg.data(), wnfft.data(), o->Scale_off ? 1 : 0,
+                          pxx.data(), freqs.data(), &lpo),
+        "PwelchBatch");
+  std::vector<std::vector<double>> rows(channels);
+  for (size_t c = 0; c < channels; ++c)
+    rows[c].assign(pxx.begin() + c * lp, pxx.begin() + c * lp + (size_t)lpo);
+  freqs.resize((size_t)lpo);
+  return {rows, freqs};
 }
 
 // Pwelch split over `devices` (empty: the device set): segment shards and one

@@ -71,6 +71,42 @@ def Pwelch(x, Fs: float, o: Optional[PwelchOptions]):
     return pxx[:lpo.value], freqs[:lpo.value]
 
 
+def pwelch_batch_fused(channels: int, n: int, nfft: int = 0, pad: int = 0,
+                       noverlap: int = 0) -> bool:
+    """Whether a batched Pwelch of this shape runs the kernel over all
+    channels (True) or the loop over the channels (gdsp_pwelch_batch_fused)."""
+    return bool(lib().gdsp_pwelch_batch_fused(int(channels), int(n), int(nfft), int(pad),
+                                              int(noverlap)))
+
+
+def PwelchBatch(rows, Fs: float, o: Optional[PwelchOptions]):
+    """spectral.Pwelch of every row of `rows` (equal lengths: the channels of
+    a recording) in one call (gdsp_pwelch_batch). Returns (Pxx[channels, lp],
+    freqs); row c equals Pwelch(rows[c], Fs, o)."""
+    if isinstance(rows, np.ndarray) and rows.ndim == 2:
+        x = np.ascontiguousarray(rows, dtype=np.float64)
+    else:
+        rs = [np.asarray(r, dtype=np.float64).reshape(-1) for r in rows]
+        if any(r.size != rs[0].size for r in rs):
+            raise Panic(_lib.GDSP_ERR_RAGGED, "ragged input array")
+        x = np.ascontiguousarray(rs, dtype=np.float64).reshape(len(rs), rs[0].size if rs else 0)
+    channels, n = x.shape
+    if n == 0:  # pwelch.go:75-77, before the options are looked at
+        return np.zeros((channels, 0)), np.zeros(0)
+    nfft, pad, noverlap, wf, scaling = resolve_options(o)
+    flen = max(pad, nfft)
+    win_seg = np.ascontiguousarray(wf(flen), dtype=np.float64)
+    win_nfft = np.ascontiguousarray(wf(nfft), dtype=np.float64)
+    lp = pad // 2 + 1
+    pxx = np.empty((channels, lp), np.float64)
+    freqs = np.empty(lp, np.float64)
+    lpo = _lib._I64(0)
+    check(lib().gdsp_pwelch_batch(_p(x), channels, n, n, float(Fs), nfft, pad, noverlap,
+                                  _p(win_seg), _p(win_nfft), int(not scaling), _p(pxx),
+                                  _p(freqs), lpo), "PwelchBatch")
+    return pxx, freqs
+
+
 def finalize(acc: np.ndarray, nsegs: int, nfft: int, pad: int, win_nfft: np.ndarray, Fs: float,
              scale_off: bool):
     """Host finalisation (gdsp_pwelch_finalize, spectral/pwelch.go:113-142) of

@@ -187,6 +187,54 @@ def device_floats(raw_dev, count: int, audio_format: int, bits: int, out=None, s
     return out
 
 
+def device_floats_planar(raw_dev, frames: int, channels: int, audio_format: int, bits: int,
+                         out=None, stream=None):
+    """device_floats for a multi-channel data chunk: `frames` interleaved
+    frames of `channels` samples from a uint8 CUDA tensor into a (channels,
+    frames) float64 CUDA tensor, out[c, i] = sample c of frame i
+    (gdsp_wav_read_floats_planar_device). out: any row stride >= frames."""
+    import torch
+
+    from . import device
+    _format_ok(audio_format, bits)
+    assert raw_dev.is_cuda and raw_dev.dtype == torch.uint8 and raw_dev.is_contiguous()
+    assert raw_dev.numel() >= frames * channels * (4 if audio_format == wavFormatIEEEFloat
+                                                   else bits // 8)
+    if out is None:
+        out = torch.empty((channels, frames), dtype=torch.float64, device=raw_dev.device)
+    assert out.dtype == torch.float64 and tuple(out.shape) == (channels, frames)
+    assert frames == 0 or out.stride(1) == 1
+    ld = out.stride(0) if channels > 1 else frames
+    with torch.cuda.device(raw_dev.device):
+        check(lib().gdsp_wav_read_floats_planar_device(
+            ctypes.c_void_p(raw_dev.data_ptr()), frames, channels, audio_format, bits,
+            ctypes.c_void_p(out.data_ptr()), ld, device._stream_ptr(stream, raw_dev.device)),
+            "wav_read_floats_planar_device")
+    return out
+
+
+def PwelchChannels(w: Wav, frames: int, o, Fs: float = 0.0):
+    """The per-channel spectra of a multi-channel file: the next `frames`
+    frames of w (frames * w.NumChannels samples), decoded planar on the GPU
+    and run through device.pwelch_batch. Returns (Pxx[NumChannels, lp],
+    freqs) as numpy arrays; row c equals spectral.Pwelch(float64(
+    w.ReadFloats(frames * C))[c::C], Fs, o). Fs defaults to w.SampleRate."""
+    import torch
+
+    from . import device
+    spectral.resolve_options(o)
+    C = int(w.NumChannels)
+    raw, _ = w._read_raw(frames * C)
+    if frames == 0:  # pwelch.go:75-77
+        return np.zeros((C, 0)), np.zeros(0)
+    fs = float(Fs or w.SampleRate)
+    dev = torch.device("cuda", torch.cuda.current_device())
+    rd = torch.frombuffer(bytearray(raw), dtype=torch.uint8).to(dev)
+    x = device_floats_planar(rd, frames, C, w.AudioFormat, w.BitsPerSample)
+    pxx, freqs = device.pwelch_batch(x, fs, o)
+    return pxx.cpu().numpy(), freqs
+
+
 def Pwelch(w: Wav, n: int, o, Fs: float = 0.0):
     """The feeder end to end: the next n samples of w, decoded on the GPU
     into float64 and run through the device Pwelch (no host float pass);

@@ -85,3 +85,73 @@ func Pwelch(x []float64, Fs float64, o *PwelchOptions) (Pxx, freqs []float64) {
 	}
 	return Pxx[:got], freqs[:got]
 }
+
+// PwelchBatch is Pwelch of every row of x (rows of equal length: the channels
+// of a recording) in one call (gdsp_pwelch_batch; no reference equivalent):
+// Pxx[c] is Pwelch(x[c], Fs, o). Rows of different lengths panic with "ragged
+// input array", as fft.FFT2 does. The rows are flattened into one C buffer,
+// so no Go pointer to a Go pointer crosses the cgo boundary.
+func PwelchBatch(x [][]float64, Fs float64, o *PwelchOptions) (Pxx [][]float64, freqs []float64) {
+	n := 0
+	if len(x) > 0 {
+		n = len(x[0])
+	}
+	for _, r := range x {
+		if len(r) != n {
+			panic("ragged input array")
+		}
+	}
+	Pxx = make([][]float64, len(x))
+	if n == 0 {
+		for c := range Pxx {
+			Pxx[c] = []float64{}
+		}
+		return Pxx, []float64{}
+	}
+	nfft, pad, wf := o.NFFT, o.Pad, o.Window
+	if nfft == 0 {
+		nfft = 256
+	}
+	if wf == nil {
+		wf = window.Hann
+	}
+	if pad == 0 {
+		pad = nfft
+	}
+	flen := nfft
+	if pad > flen {
+		flen = pad
+	}
+	wseg, wnfft := wf(flen), wf(nfft)
+	lp := pad/2 + 1
+	flat := make([]float64, len(x)*n)
+	for c, r := range x {
+		copy(flat[c*n:], r)
+	}
+	out := make([]float64, len(x)*lp)
+	freqs = make([]float64, lp)
+	scaleOff := C.int(0)
+	if o.Scale_off {
+		scaleOff = 1
+	}
+	var got C.int64_t
+	st := C.gdsp_pwelch_batch((*C.double)(unsafe.Pointer(&flat[0])), C.int64_t(len(x)),
+		C.int64_t(n), C.int64_t(n), C.double(Fs), C.int64_t(nfft), C.int64_t(pad),
+		C.int64_t(o.Noverlap), (*C.double)(unsafe.Pointer(&wseg[0])),
+		(*C.double)(unsafe.Pointer(&wnfft[0])), scaleOff, (*C.double)(unsafe.Pointer(&out[0])),
+		(*C.double)(unsafe.Pointer(&freqs[0])), &got)
+	switch st {
+	case C.GDSP_OK:
+	case C.GDSP_ERR_DIVIDE_BY_ZERO:
+		panic(C.GoString(C.gdsp_status_string(st)))
+	case C.GDSP_ERR_INVALID:
+		panic(C.GoString(C.gdsp_last_error()))
+	default:
+		panic("gdspfft: " + C.GoString(C.gdsp_status_string(st)) + ": " +
+			C.GoString(C.gdsp_last_error()))
+	}
+	for c := range Pxx {
+		Pxx[c] = out[c*lp : c*lp+int(got)]
+	}
+	return Pxx, freqs[:got]
+}

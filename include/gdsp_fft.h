@@ -99,7 +99,11 @@ enum {
    * (FFT, row multiply, IFFT: three kernels) also for the powers of 2 the
    * fused one-kernel convolution serves. Read when the call is made, not
    * when the plan is built. */
-  GDSP_ALGO_NO_FUSED_CONVOLVE = 64
+  GDSP_ALGO_NO_FUSED_CONVOLVE = 64,
+  /* gdsp_pwelch_batch / gdsp_pwelch_batch_accumulate_device as a loop of
+   * gdsp_pwelch_accumulate_device over the channels also for the lengths the
+   * batched kernel serves. Read when the call is made. */
+  GDSP_ALGO_NO_FUSED_PWELCH_BATCH = 128
 };
 /* Unknown bits → GDSP_ERR_INVALID (the selection is left unchanged). */
 int gdsp_set_algorithm(unsigned flags);
@@ -190,6 +194,31 @@ int gdsp_segment_count(int64_t lx, int64_t size, int64_t noverlap, int64_t *coun
 int gdsp_pwelch(const double *x, int64_t n, double fs, int64_t nfft, int64_t pad,
                 int64_t noverlap, const double *win_seg, const double *win_nfft,
                 int scale_off, double *pxx, double *freqs, int64_t *lp_out);
+
+/* Additive batched spectral.Pwelch (no reference equivalent): `channels`
+ * signals of n float64 each, channel c at x + c*ldx (ldx >= n), one set of
+ * options for all. Row c of pxx (channels × lp, lp = pad/2+1) is what
+ * gdsp_pwelch defines for x + c*ldx: the same defaults, NULL windows = Hann, a
+ * channel shorter than nfft zero-padded to nfft. freqs: lp float64, once.
+ * n == 0 → *lp_out = 0, GDSP_OK; channels == 0 → GDSP_OK, only freqs and
+ * *lp_out written. channels < 0, n < 0, ldx < n with channels > 1, or a needed
+ * NULL pointer → GDSP_ERR_INVALID; a zero stride → GDSP_ERR_DIVIDE_BY_ZERO as
+ * from gdsp_segment_count; all answered before any device call. Runs on the
+ * current device (a batch is not split over the device set). F = max(pad,
+ * nfft) a power of 2 from 64 to 2048 runs one fused kernel over all channels;
+ * every other length loops over the channels inside the library, which is
+ * one call but no faster than calling gdsp_pwelch per channel. */
+int gdsp_pwelch_batch(const double *x, int64_t channels, int64_t n, int64_t ldx, double fs,
+                      int64_t nfft, int64_t pad, int64_t noverlap, const double *win_seg,
+                      const double *win_nfft, int scale_off, double *pxx, double *freqs,
+                      int64_t *lp_out);
+/* 1: a gdsp_pwelch_batch / gdsp_pwelch_batch_accumulate_device call of this
+ * shape (0 = the defaults, as gdsp_pwelch) runs the batched kernel under the
+ * current flags; 0: the loop over the channels (F < 64, F = 4096 and up,
+ * non-powers of 2, strides above 2^22, GDSP_ALGO_NO_FUSED_PWELCH_BATCH). Host
+ * arithmetic only (no GPU needed). */
+int gdsp_pwelch_batch_fused(int64_t channels, int64_t n, int64_t nfft, int64_t pad,
+                            int64_t noverlap);
 
 /* window.Hann — window/window.go:62-76, as a host table generator used by the
  * shim for the default window (L float64 written to out). */
@@ -376,6 +405,36 @@ int gdsp_pwelch_accumulate_device(const double *d_x, int64_t n, int64_t nfft, in
 int gdsp_pwelch_finalize(const double *acc, int64_t flen, int64_t nsegs, int64_t nfft,
                          int64_t pad, const double *win_nfft, double fs, int scale_off,
                          double *pxx, double *freqs);
+
+/* gdsp_pwelch_accumulate_device over the channels of a planar device batch:
+ * channel c is n float64 at d_x + c*ldx (ldx >= n, any value: odd ones too),
+ * and its sums are added into d_acc + c*flen (channels × flen, zeroed by the
+ * caller before the first call). The same segments [seg_begin, seg_end) of
+ * every channel; geometry checks as gdsp_pwelch_accumulate_device, plus
+ * channels < 0, n < 0 or ldx < n with channels > 1 → GDSP_ERR_INVALID.
+ * Lengths and fallback as gdsp_pwelch_batch (gdsp_pwelch_batch_fused). */
+int gdsp_pwelch_batch_accumulate_device(const double *d_x, int64_t channels, int64_t n,
+                                        int64_t ldx, int64_t nfft, int64_t pad, int64_t noverlap,
+                                        int64_t seg_begin, int64_t seg_end,
+                                        const double *d_win_seg, double *d_acc, void *stream);
+
+/* gdsp_pwelch_finalize on the device, per channel: d_acc channels × flen
+ * summed accumulators → d_pxx channels × (pad/2+1), the host function's
+ * operations in its order (bit-identical results). win_nfft: host table of
+ * nfft (NULL = Hann); freqs: host buffer of pad/2+1 (may be NULL). Stream-
+ * ordered; the PSDs never leave the device. */
+int gdsp_pwelch_batch_finalize_device(const double *d_acc, int64_t channels, int64_t flen,
+                                      int64_t nsegs, int64_t nfft, int64_t pad,
+                                      const double *win_nfft, double fs, int scale_off,
+                                      double *d_pxx, double *freqs, void *stream);
+
+/* gdsp_wav_read_floats_device for a multi-channel data chunk, into planar
+ * float64 rows: d_out[c*ld_out + i] = the widened float32 of sample c of
+ * frame i (d_in[i*channels + c]), i < frames, c < channels <= 65535, ld_out
+ * >= frames. Format errors as gdsp_wav_read_floats_device. */
+int gdsp_wav_read_floats_planar_device(const void *d_in, int64_t frames, int64_t channels,
+                                       int audio_format, int bits_per_sample, double *d_out,
+                                       int64_t ld_out, void *stream);
 
 /* gdsp_wav_read_floats on device buffers (d_in: the raw data-chunk bytes at
  * any alignment; d_out: count float32 or float64), stream-ordered: decode a
