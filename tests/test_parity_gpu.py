@@ -708,7 +708,8 @@ def test_chirpz6k_large_batch_properties(gdsp, n, batch):
     y = D.fft_batch(x, chirpz=True)
     z = D.fft_batch(y, inverse=True, chirpz=True)
     err = ((z - x).abs().amax(dim=1) / x.abs().amax(dim=1)).max().item()
-    # (the reference's unreduced chirp angle, bluestein.go:53: ~1e-12 above n = 4096)
+    # (bounds from when the chirp kept the reference's unreduced angle, bluestein.go:53:
+    # ~1e-12 above n = 4096; tests/test_accuracy_gpu.py holds the tighter ones)
     assert err < (1e-12 if n <= 3200 else 1e-11), err
     y2 = D.fft_batch(2.0 * x[:64] - 1j * x[64:128], chirpz=True)
     lin = ((y2 - (2.0 * y[:64] - 1j * y[64:128])).abs().max() / y[:128].abs().max()).item()
@@ -1141,7 +1142,7 @@ def test_ensure_radix2_factors_then_fft(gdsp, oracle, n):
     rng = np.random.default_rng(n)
     x = rng.standard_normal(n) + 1j * rng.standard_normal(n)
     assert nrel(gdsp.fft.FFT(x), oracle.fft(x)) < (1e-8 if n > 2000000 else 1e-9)
-    # chirp-z lengths carry the reference's unreduced chirp angle (~1e-12 at 8209)
+    # (a bound from when the chirp kept the reference's unreduced angle, ~1e-12 at 8209)
     assert nrel(gdsp.fft.IFFT(gdsp.fft.FFT(x)), x) < 1e-11
 
 
@@ -1554,7 +1555,7 @@ def _blufix_checks(gdsp, oracle, D, F, n):
         ref = oracle.fft_rows(x)
         y = gdsp.fft.FFTBatch(x)
         assert row_nrel(y, ref) < TOL
-        assert row_nrel(y, np.fft.fft(x, axis=1)) < 1e-11  # the chirp's unreduced angle (bluestein.go:53)
+        assert row_nrel(y, np.fft.fft(x, axis=1)) < 1e-11  # (set when the chirp's angle was not reduced, bluestein.go:53)
         assert row_nrel(gdsp.fft.FFTBatch(x, inverse=True), oracle.ifft_rows(x)) < TOL
         xr = rng.uniform(-1, 1, (batch, n))
         assert row_nrel(gdsp.fft.FFTRealBatch(xr), oracle.fft_rows(xr.astype(np.complex128))) < TOL
