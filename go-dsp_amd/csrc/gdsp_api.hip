@@ -67,7 +67,8 @@ std::atomic<unsigned> g_algo{GDSP_ALGO_DEFAULT};
 constexpr unsigned kAlgoAll = GDSP_ALGO_GENERIC_MIXED | GDSP_ALGO_NO_CHIRPZ_PARTS |
                               GDSP_ALGO_CHIRPZ_POW2 | GDSP_ALGO_CHIRPZ_UNFUSED |
                               GDSP_ALGO_NO_RADER | GDSP_ALGO_NO_RACE |
-                              GDSP_ALGO_NO_FUSED_CONVOLVE | GDSP_ALGO_NO_FUSED_PWELCH_BATCH;
+                              GDSP_ALGO_NO_FUSED_CONVOLVE | GDSP_ALGO_NO_FUSED_PWELCH_BATCH |
+                              GDSP_ALGO_NO_FUSED_CPSD;
 
 // Scratch device memory: a grow-only buffer per (device, stream, use-site
 // slot), allocated with hipMalloc. Reuse is ordered by the stream itself: a
@@ -81,7 +82,8 @@ constexpr unsigned kAlgoAll = GDSP_ALGO_GENERIC_MIXED | GDSP_ALGO_NO_CHIRPZ_PART
 enum Slot {
   SLOT_IN = 0, SLOT_OUT, SLOT_AUX, SLOT_AUX2, SLOT_GLOBAL, SLOT_GLOBAL_IN, SLOT_REAL,
   SLOT_BLU, SLOT_FFT2, SLOT_PW_PART, SLOT_PW_RED, SLOT_PW_BUF, SLOT_FS0, SLOT_FS1, SLOT_FS2,
-  SLOT_FS3, SLOT_FFTN, SLOT_MX0, SLOT_MX1, SLOT_PARTS, SLOT_CONV, SLOT_COUNT
+  SLOT_FS3, SLOT_FFTN, SLOT_MX0, SLOT_MX1, SLOT_PARTS, SLOT_CONV, SLOT_CP_Y, SLOT_CP_OUT, SLOT_CP_BAL,
+  SLOT_COUNT
 };
 
 struct Workspace {
@@ -1698,6 +1700,237 @@ int gdsp_pwelch_batch(const double *x, int64_t channels, int64_t n, int64_t ldx,
   for (int64_t c = 0; c < channels; ++c)
     STCHK(gdsp_pwelch_finalize(acc.data() + c * flen, flen, nsegs, nfft, pad, win_nfft, fs,
                                scale_off, pxx + c * lp, freqs));
+  *lp_out = lp;
+  return GDSP_OK;
+}
+
+// ---- batched cross spectra: Cpsd and coherence of x channels against y --------
+// The fused kernel (cpsd_batch.hip) serves the lengths of the batched Pwelch;
+// every other length and stride, and any shape under GDSP_ALGO_NO_FUSED_CPSD,
+// runs the materialised form. Host arithmetic only.
+static bool cpsd_batch_fused(int64_t flen, int64_t stride) {
+  return flen > 0 && gdsp_api::is_pow2(flen) && gdsp::cpsd_batch_applies(gdsp_api::ilog2(flen)) &&
+         stride <= ((int64_t)1 << 22) && !(g_algo.load() & GDSP_ALGO_NO_FUSED_CPSD);
+}
+
+int gdsp_cpsd_batch_fused(int64_t channels, int64_t n, int64_t nfft, int64_t pad,
+                          int64_t noverlap) {
+  if (channels < 0 || n < 0) return 0;
+  if (nfft == 0) nfft = 256;
+  if (pad == 0) pad = nfft;
+  if (nfft < 0 || pad < 0) return 0;
+  return cpsd_batch_fused(pad > nfft ? pad : nfft, nfft - noverlap) ? 1 : 0;
+}
+
+int gdsp_cpsd_batch_accumulate_device(const double *d_x, int64_t ldx, const double *d_y,
+                                      int64_t ldy, int64_t y_rows, int64_t channels, int64_t n,
+                                      int64_t nfft, int64_t pad, int64_t noverlap,
+                                      int64_t seg_begin, int64_t seg_end,
+                                      const double *d_win_seg, double *d_acc, void *stream) {
+  if (nfft <= 0 || pad <= 0 || seg_begin < 0 || seg_end < seg_begin)
+    return fail(GDSP_ERR_INVALID, "bad Cpsd geometry");
+  if (channels < 0 || n < 0 || y_rows < 0 || (channels > 1 && ldx < n) || (y_rows > 1 && ldy < n))
+    return fail(GDSP_ERR_INVALID, "bad batch geometry");
+  if (y_rows != 1 && y_rows != channels)
+    return fail(GDSP_ERR_UNEQUAL, "y is neither one row nor a row per channel");
+  const int64_t stride = nfft - noverlap;
+  // Segment divides by the stride only where there is more than one segment
+  if (stride == 0 && seg_end > 1) return fail(GDSP_ERR_DIVIDE_BY_ZERO, "integer divide by zero");
+  if (channels == 0 || seg_end == seg_begin) return GDSP_OK;
+  if (!d_x || !d_y || !d_win_seg || !d_acc) return fail(GDSP_ERR_INVALID, "NULL pointer");
+  // a negative stride (Noverlap > NFFT) leaves at most segment 0 (Segment)
+  if ((seg_end - 1) * stride + nfft > n || (stride < 0 && seg_end > 1))
+    return fail(GDSP_ERR_INVALID, "segments exceed the signal");
+  const int64_t flen = pad > nfft ? pad : nfft;
+  const int64_t hb = flen / 2 + 1, nseg = seg_end - seg_begin;
+  const int64_t ldyk = y_rows == 1 ? 0 : ldy;  // the kernels' y row stride
+  hipStream_t s = (hipStream_t)stream;
+  gdsp_plan *p = nullptr;
+  STCHK(get_plan(flen, &p));
+  DevBuf buf, part, red, bal;
+  // get_plan builds a power of 2 up to 2^14 as KIND_LDS under every flag set
+  // (build_plan, plan.hip), so gdsp_cpsd_batch_fused's answer holds here; the
+  // kind is checked because the kernel reads that plan's twiddle table
+  if (cpsd_batch_fused(flen, stride) && p->kind == KIND_LDS) {
+    int64_t wpc = 0, gpw = 0, rows = 0;
+    gdsp::cpsd_batch_geometry(p->log2n, channels, nseg, &wpc, &gpw, &rows);
+    // channels per launch: the partials within 512 MiB
+    int64_t cpl = ((int64_t)1 << 26) / (rows * 4 * hb);
+    if (cpl < 1) cpl = 1;
+    if (cpl > channels) cpl = channels;
+    STCHK(part.alloc((size_t)cpl * (size_t)rows * (size_t)(4 * hb) * sizeof(double), s,
+                     SLOT_PW_PART));
+    STCHK(red.alloc((size_t)gdsp::reduce_batch_scratch_doubles(cpl, rows, 4 * hb) * sizeof(double),
+                    s, SLOT_PW_RED));
+    for (int64_t c0 = 0; c0 < channels; c0 += cpl) {
+      const int64_t nc = channels - c0 < cpl ? channels - c0 : cpl;
+      HIPCHK(gdsp::launch_cpsd_batch(p->log2n, d_x + c0 * ldx, ldx, d_y + c0 * ldyk, ldyk, nc, wpc,
+                                     nfft, stride, seg_begin, seg_end, gpw, d_win_seg, p->tw,
+                                     (double *)part.p, s));
+      HIPCHK(gdsp::launch_reduce_batch((const double *)part.p, nc, rows, 4 * hb,
+                                       d_acc + c0 * 4 * hb, (double *)red.p, s));
+    }
+    return GDSP_OK;
+  }
+  // materialised form: chunks of at most 512 MiB of complex rows, whole
+  // channels where a channel's segments fit, else one channel's segments in
+  // runs; parts of kRpp rows, reduced in the fixed order
+  constexpr int64_t kRpp = 64;
+  int64_t maxrows = ((int64_t)1 << 25) / flen;
+  if (maxrows < 1) maxrows = 1;
+  const int64_t ns_max = nseg < maxrows ? nseg : maxrows;  // segments per run
+  int64_t cpl = maxrows / ns_max;                           // channels per launch
+  if (cpl > channels) cpl = channels;
+  const int64_t parts_max = (ns_max + kRpp - 1) / kRpp;
+  STCHK(buf.alloc((size_t)cpl * (size_t)ns_max * (size_t)flen * sizeof(cd), s, SLOT_PW_BUF));
+  STCHK(bal.alloc((size_t)cpl * (size_t)ns_max * sizeof(double), s, SLOT_CP_BAL));
+  double *alpha = (double *)bal.p;  // a power of 2 per row (cpsd_batch.hip, Balance)
+  STCHK(part.alloc((size_t)cpl * (size_t)parts_max * (size_t)(4 * hb) * sizeof(double), s,
+                   SLOT_PW_PART));
+  STCHK(red.alloc((size_t)gdsp::reduce_batch_scratch_doubles(cpl, parts_max, 4 * hb) *
+                      sizeof(double),
+                  s, SLOT_PW_RED));
+  for (int64_t c0 = 0; c0 < channels; c0 += cpl) {
+    const int64_t nc = channels - c0 < cpl ? channels - c0 : cpl;
+    for (int64_t j0 = 0; j0 < nseg; j0 += ns_max) {
+      const int64_t ns = nseg - j0 < ns_max ? nseg - j0 : ns_max;
+      HIPCHK(gdsp::launch_cpsd_balance(d_x + c0 * ldx, ldx, d_y + c0 * ldyk, ldyk, nc, ns, nfft,
+                                       stride, seg_begin + j0, d_win_seg, alpha, s));
+      HIPCHK(gdsp::launch_cpsd_gather(d_x + c0 * ldx, ldx, d_y + c0 * ldyk, ldyk, nc, ns, nfft,
+                                      flen, stride, seg_begin + j0, d_win_seg, alpha,
+                                      (cd *)buf.p, s));
+      STCHK(exec_plan(p, buf.p, (cd *)buf.p, nc * ns, false, gdsp::LOAD_COMPLEX, s));
+      HIPCHK(gdsp::launch_cpsd_partials((const cd *)buf.p, nc, ns, flen, kRpp, alpha,
+                                        (double *)part.p, s));
+      HIPCHK(gdsp::launch_reduce_batch((const double *)part.p, nc, (ns + kRpp - 1) / kRpp, 4 * hb,
+                                       d_acc + c0 * 4 * hb, (double *)red.p, s));
+    }
+  }
+  return GDSP_OK;
+}
+
+// the window's norm (spectral/pwelch.go:124-132) and the frequencies (:138-142)
+static double cpsd_norm_freqs(const double *win_nfft, int64_t nfft, int64_t pad, double fs,
+                              int scale_off, double *freqs) {
+  std::vector<double> hw;
+  if (!win_nfft) {
+    hw.resize((size_t)nfft);
+    hann_table(nfft, hw.data());
+    win_nfft = hw.data();
+  }
+  double norm = 0;  // as gdsp_pwelch_finalize
+  for (int64_t i = 0; i < nfft; ++i) norm += win_nfft[i] * win_nfft[i];
+  if (!scale_off) norm *= fs;
+  if (freqs) {
+    const double coef = fs / (double)pad;
+    for (int64_t j = 0; j < pad / 2 + 1; ++j) freqs[j] = (double)j * coef;
+  }
+  return norm;
+}
+
+int gdsp_cpsd_batch_finalize_device(const double *d_acc, int64_t channels, int64_t flen,
+                                    int64_t nsegs, int64_t nfft, int64_t pad,
+                                    const double *win_nfft, double fs, int scale_off,
+                                    void *d_pxy, double *d_pxx, double *d_pyy, double *d_coh,
+                                    double *freqs, void *stream) {
+  if (channels < 0 || flen <= 0 || nfft <= 0 || pad <= 0 || nsegs < 0)
+    return fail(GDSP_ERR_INVALID, "bad argument");
+  if (channels > 0 && !d_acc) return fail(GDSP_ERR_INVALID, "NULL pointer");
+  const int64_t lp = pad / 2 + 1, hb = flen / 2 + 1;
+  if (lp > hb) return fail(GDSP_ERR_INVALID, "accumulators shorter than Pad / 2 + 1");
+  const double norm = cpsd_norm_freqs(win_nfft, nfft, pad, fs, scale_off, freqs);
+  if (channels == 0 || (!d_pxy && !d_pxx && !d_pyy && !d_coh)) return GDSP_OK;
+  HIPCHK(gdsp::launch_cpsd_finalize(d_acc, channels, hb, lp, nsegs, norm, (cd *)d_pxy, d_pxx,
+                                    d_pyy, d_coh, (hipStream_t)stream));
+  return GDSP_OK;
+}
+
+int gdsp_cpsd_batch(const double *x, int64_t ldx, const double *y, int64_t ldy, int64_t y_rows,
+                    int64_t channels, int64_t n, double fs, int64_t nfft, int64_t pad,
+                    int64_t noverlap, const double *win_seg, const double *win_nfft,
+                    int scale_off, double *pxy, double *pxx, double *pyy, double *coh,
+                    double *freqs, int64_t *lp_out) {
+  if (!lp_out) return fail(GDSP_ERR_INVALID, "NULL pointer");
+  *lp_out = 0;
+  if (channels < 0 || n < 0 || y_rows < 0) return fail(GDSP_ERR_INVALID, "negative size");
+  if (n == 0) return GDSP_OK;
+  if (y_rows != 1 && y_rows != channels)
+    return fail(GDSP_ERR_UNEQUAL, "y is neither one row nor a row per channel");
+  if (nfft == 0) nfft = 256;
+  if (pad == 0) pad = nfft;
+  if (nfft < 0 || pad < 0) return fail(GDSP_ERR_INVALID, "negative NFFT/Pad");
+  if ((channels > 1 && ldx < n) || (y_rows > 1 && ldy < n))
+    return fail(GDSP_ERR_INVALID, "row stride below the channel length");
+  const int64_t lx = n < nfft ? nfft : n;  // dsputils.ZeroPadF(x, nfft) per channel
+  int64_t nsegs = 0;
+  STCHK(segment_count(lx, nfft, noverlap, &nsegs));
+  if (!freqs || (channels > 0 && (!x || !y || !pxy))) return fail(GDSP_ERR_INVALID, "NULL pointer");
+  const int64_t flen = pad > nfft ? pad : nfft;
+  const int64_t lp = pad / 2 + 1, hb = flen / 2 + 1;
+  if (channels == 0) {
+    (void)cpsd_norm_freqs(win_nfft, nfft, pad, fs, scale_off, freqs);
+    *lp_out = lp;
+    return GDSP_OK;
+  }
+  std::vector<double> hseg;
+  if (!win_seg) {
+    hseg.resize((size_t)flen);
+    hann_table(flen, hseg.data());
+    win_seg = hseg.data();
+  }
+  int dev = 0;
+  STCHK(current_device(&dev));
+  hipStream_t s = thread_stream(dev);
+  if (!s) return fail(GDSP_ERR_HIP, "stream creation failed");
+  const size_t rowb = (size_t)lx * sizeof(double);
+  const size_t abytes = (size_t)channels * (size_t)(4 * hb) * sizeof(double);
+  const size_t cl = (size_t)channels * (size_t)lp;
+  // outputs in one buffer: pxy (2 cl doubles), then pxx, pyy, coh where asked
+  double *const outs[3] = {pxx, pyy, coh};
+  size_t ndbl = 2 * cl;
+  for (double *o : outs) ndbl += o ? cl : 0;
+  DevBuf dx, dy, dw, dacc, dout;
+  STCHK(dx.alloc((size_t)channels * rowb, s, SLOT_IN));
+  STCHK(dy.alloc((size_t)y_rows * rowb, s, SLOT_CP_Y));
+  STCHK(dw.alloc((size_t)flen * sizeof(double), s, SLOT_AUX));
+  STCHK(dacc.alloc(abytes, s, SLOT_AUX2));
+  STCHK(dout.alloc(ndbl * sizeof(double), s, SLOT_CP_OUT));
+  double *px = (double *)dx.p, *py = (double *)dy.p, *po = (double *)dout.p;
+  double *dev_out[3] = {nullptr, nullptr, nullptr};
+  size_t off = 2 * cl;
+  for (int i = 0; i < 3; ++i)
+    if (outs[i]) {
+      dev_out[i] = po + off;
+      off += cl;
+    }
+  // rows of lx on the device, a short signal zero-padded (pwelch.go:97-99)
+  auto stage = [&](double *d, const double *h, int64_t rows, int64_t ld) -> int {
+    if (lx > n) HIPCHK(hipMemsetAsync(d, 0, (size_t)rows * rowb, s));
+    if (lx == n && (ld == n || rows == 1)) return copy_h2d(d, h, (size_t)rows * rowb, s);
+    for (int64_t c = 0; c < rows; ++c)
+      STCHK(copy_h2d(d + c * lx, h + c * ld, (size_t)n * sizeof(double), s));
+    return GDSP_OK;
+  };
+  auto queue = [&]() -> int {
+    STCHK(stage(px, x, channels, ldx));
+    STCHK(stage(py, y, y_rows, ldy));
+    STCHK(copy_h2d(dw.p, win_seg, (size_t)flen * sizeof(double), s));
+    HIPCHK(hipMemsetAsync(dacc.p, 0, abytes, s));
+    STCHK(gdsp_cpsd_batch_accumulate_device(px, lx, py, lx, y_rows, channels, lx, nfft, pad,
+                                            noverlap, 0, nsegs, (const double *)dw.p,
+                                            (double *)dacc.p, s));
+    return gdsp_cpsd_batch_finalize_device((const double *)dacc.p, channels, flen, nsegs, nfft,
+                                           pad, win_nfft, fs, scale_off, po, dev_out[0],
+                                           dev_out[1], dev_out[2], freqs, s);
+  };
+  const int st = queue();
+  if (st != GDSP_OK) {
+    (void)hipStreamSynchronize(s);  // queued copies still read the staging halves
+    return st;
+  }
+  STCHK(copy_d2h(pxy, po, 2 * cl * sizeof(double), s));
+  for (int i = 0; i < 3; ++i)
+    if (outs[i]) STCHK(copy_d2h(outs[i], dev_out[i], cl * sizeof(double), s));
   *lp_out = lp;
   return GDSP_OK;
 }

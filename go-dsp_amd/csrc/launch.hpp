@@ -83,6 +83,38 @@ hipError_t launch_reduce_batch(const double *partial, int64_t channels, int64_t 
                                double *acc, double *scratch, hipStream_t s);
 hipError_t launch_pwelch_finalize(const double *acc, int64_t channels, int64_t flen, int64_t lp,
                                   int64_t nsegs, double norm, double *pxx, hipStream_t s);
+// the cross-spectral sums of two planar batches (cpsd_batch.hip): x channel c
+// at x + c ldx, y channel c at y + c ldy (ldy = 0: one y for all), one segment
+// of both per transform. The fused kernel for the lengths of the batched
+// Pwelch, into partial[channel][rows][4][hb] (hb = F / 2 + 1; planes Sxx, Syy,
+// Re Sxy, Im Sxy; reduced by launch_reduce_batch with F := 4 hb); the
+// materialised form for every other length (rows w x_s + i w y_s of segments
+// [seg0, seg0 + ns) of every channel, then, after the plan's transform, the
+// sums of each row and its mirror over parts of rpp rows); and the finaliser
+// of acc[channel][4][hb] into any of pxy, pxx, pyy, coh [channel][lp].
+// Every segment's y is packed times a power of 2 that is taken out of its
+// products again (cpsd_batch.hip, Balance): inside the fused kernel; in the
+// materialised form alpha[row] from launch_cpsd_balance, rows as the gather's
+bool cpsd_batch_applies(int log2f);
+void cpsd_batch_geometry(int log2f, int64_t channels, int64_t nsegs, int64_t *wpc, int64_t *gpw,
+                         int64_t *rows);
+hipError_t launch_cpsd_batch(int log2f, const double *x, int64_t ldx, const double *y, int64_t ldy,
+                             int64_t channels, int64_t wpc, int64_t nfft, int64_t stride,
+                             int64_t seg_begin, int64_t seg_end, int64_t gpw, const double *win,
+                             const cd *tw, double *partial, hipStream_t s);
+hipError_t launch_cpsd_balance(const double *x, int64_t ldx, const double *y, int64_t ldy,
+                               int64_t channels, int64_t ns, int64_t nfft, int64_t stride,
+                               int64_t seg0, const double *win, double *alpha, hipStream_t s);
+hipError_t launch_cpsd_gather(const double *x, int64_t ldx, const double *y, int64_t ldy,
+                              int64_t channels, int64_t ns, int64_t nfft, int64_t flen,
+                              int64_t stride, int64_t seg0, const double *win,
+                              const double *alpha, cd *buf, hipStream_t s);
+hipError_t launch_cpsd_partials(const cd *buf, int64_t channels, int64_t ns, int64_t flen,
+                                int64_t rpp, const double *alpha, double *partial,
+                                hipStream_t s);
+hipError_t launch_cpsd_finalize(const double *acc, int64_t channels, int64_t hb, int64_t lp,
+                                int64_t nsegs, double norm, cd *pxy, double *pxx, double *pyy,
+                                double *coh, hipStream_t s);
 // fused Pwelch on a compiled specialisation (d = the plan's specialisation
 // descriptor, d.n = max(pad, nfft)); workers per block, 0 if d is none or
 // its kernel cannot stage a pair of span = stride + nfft samples

@@ -237,6 +237,99 @@ def pwelch_batch_accumulate(x, nfft: int, pad: int, noverlap: int, seg_begin: in
     return acc
 
 
+def _cpsd_rows(x, y):
+    """(channels, n, ldx, ldy, y_rows) of a cross-spectral pair of float64
+    CUDA tensors: x (channels, n), y (n,) or x's shape; unit inner strides."""
+    torch = _torch()
+    assert x.is_cuda and x.dtype == torch.float64 and x.dim() == 2
+    assert y.is_cuda and y.dtype == torch.float64 and y.device == x.device
+    channels, n = x.shape
+    if tuple(y.shape) != (n,) and tuple(y.shape) != (channels, n):
+        raise _lib.Panic(_lib.GDSP_ERR_UNEQUAL, "arrays not of equal size")
+    assert n == 0 or (x.stride(1) == 1 and y.stride(-1) == 1), "rows must have unit inner stride"
+    ldx = x.stride(0) if channels > 1 else n
+    y_rows = 1 if y.dim() == 1 else channels
+    ldy = y.stride(0) if y_rows > 1 else n
+    assert ldx >= n and ldy >= n, "rows overlap"
+    return channels, n, ldx, ldy, y_rows
+
+
+def cpsd_batch_accumulate(x, y, nfft: int, pad: int, noverlap: int, seg_begin: int, seg_end: int,
+                          win_seg, acc, stream=None):
+    """Adds the cross-spectral sums of segments [seg_begin, seg_end) of every
+    row of x (channels, n) against y ((n,): one for all rows, or x's shape:
+    row by row) into acc: (channels, 4, max(pad, nfft) // 2 + 1) float64,
+    contiguous, planes Sxx, Syy, Re Sxy, Im Sxy with Sxy = sum conj(X_s) Y_s.
+    The true sums of the range: ranges add in any split. float64 CUDA tensors,
+    unit inner stride, any row stride (gdsp_cpsd_batch_accumulate_device)."""
+    torch = _torch()
+    channels, n, ldx, ldy, y_rows = _cpsd_rows(x, y)
+    hb = max(pad, nfft) // 2 + 1
+    assert acc.is_cuda and acc.dtype == torch.float64 and acc.is_contiguous()
+    assert acc.numel() >= channels * 4 * hb
+    assert win_seg.is_cuda and win_seg.dtype == torch.float64 and win_seg.numel() >= max(pad, nfft)
+    with torch.cuda.device(x.device):
+        check(lib().gdsp_cpsd_batch_accumulate_device(
+            _ptr(x), ldx, _ptr(y), ldy, y_rows, channels, n, nfft, pad, noverlap, seg_begin,
+            seg_end, _ptr(win_seg), _ptr(acc), _stream_ptr(stream, x.device)),
+            "cpsd_batch_accumulate")
+    return acc
+
+
+def cpsd_batch(x, y, Fs: float, o, acc=None, stream=None, out=None):
+    """spectral.CpsdBatch on float64 CUDA tensors (unit inner stride, any row
+    stride), device-resident end to end: x (channels, n) against y, (n,) or
+    x's shape. Returns spectral.CrossSpectra(Pxy complex128, Pxx, Pyy, Cxy
+    float64, each (channels, pad // 2 + 1) on x's device, freqs numpy).
+    acc: the caller's accumulator ((channels, 4, max(pad, nfft) // 2 + 1)
+    float64, contiguous; overwritten); out: the caller's (Pxy, Pxx, Pyy, Cxy)
+    tensors, contiguous, any of them None."""
+    import contextlib
+
+    import numpy as np
+
+    from . import distributed, spectral
+    torch = _torch()
+    channels, n, _, _, _ = _cpsd_rows(x, y)
+    dev = x.device
+    if n == 0:  # pwelch.go:75-77
+        e = torch.zeros((channels, 0), dtype=torch.float64, device=dev)
+        return spectral.CrossSpectra(e.to(torch.complex128), e, e.clone(), e.clone(), np.zeros(0))
+    nfft, pad, noverlap, wf, scaling = spectral.resolve_options(o)
+    flen, lp = max(pad, nfft), pad // 2 + 1
+    hb = flen // 2 + 1
+    ctx = torch.cuda.stream(stream) if stream is not None else contextlib.nullcontext()
+    with torch.cuda.device(dev), ctx:
+        if n < nfft:  # pwelch.go:97-99: zero-padded to nfft
+            x = torch.nn.functional.pad(x, (0, nfft - n))
+            y = torch.nn.functional.pad(y, (0, nfft - n))
+        nsegs = spectral.segment_count(x.shape[1], nfft, noverlap)
+        win_seg = distributed._device_window(wf, flen, dev, torch)
+        if acc is None:
+            acc = torch.zeros((channels, 4, hb), dtype=torch.float64, device=dev)
+        else:
+            assert acc.is_cuda and acc.dtype == torch.float64 and acc.is_contiguous()
+            assert acc.numel() >= channels * 4 * hb
+            acc.view(-1)[:channels * 4 * hb].zero_()
+        outs = list(out) if out is not None else [None] * 4
+        assert len(outs) == 4
+        for i, dt in enumerate((torch.complex128, torch.float64, torch.float64, torch.float64)):
+            if outs[i] is None:
+                outs[i] = torch.empty((channels, lp), dtype=dt, device=dev)
+            assert outs[i].is_cuda and outs[i].dtype == dt and outs[i].is_contiguous()
+            assert outs[i].numel() >= channels * lp
+        if nsegs > 0:
+            cpsd_batch_accumulate(x, y, nfft, pad, noverlap, 0, nsegs, win_seg, acc, stream)
+        win_nfft = np.ascontiguousarray(wf(nfft), dtype=np.float64)
+        freqs = np.empty(lp, np.float64)
+        check(lib().gdsp_cpsd_batch_finalize_device(
+            _ptr(acc), channels, flen, nsegs, nfft, pad, win_nfft.ctypes.data_as(_lib._P),
+            float(Fs), int(not scaling), _ptr(outs[0]), _ptr(outs[1]), _ptr(outs[2]),
+            _ptr(outs[3]), freqs.ctypes.data_as(_lib._P), _stream_ptr(stream, dev)),
+            "cpsd_batch_finalize")
+    return spectral.CrossSpectra(outs[0], outs[1], outs[2], outs[3], freqs)
+
+
 def pwelch_batch(x, Fs: float, o, out=None, acc=None, stream=None):
     """spectral.Pwelch of every row of a (channels, n) float64 CUDA tensor
     (unit inner stride, any row stride), device-resident end to end: returns

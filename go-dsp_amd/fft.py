@@ -227,6 +227,7 @@ ALGO_NO_RADER = 16
 ALGO_NO_RACE = 32
 ALGO_NO_FUSED_CONVOLVE = 64
 ALGO_NO_FUSED_PWELCH_BATCH = 128
+ALGO_NO_FUSED_CPSD = 256
 
 
 def SetAlgorithm(flags: int = ALGO_DEFAULT) -> None:

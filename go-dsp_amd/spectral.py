@@ -4,7 +4,7 @@ packed-pair FFT + |X|^2 accumulation) through gdsp_pwelch."""
 from __future__ import annotations
 
 from dataclasses import dataclass
-from typing import Callable, Optional
+from typing import Any, Callable, NamedTuple, Optional
 
 import numpy as np
 
@@ -105,6 +105,100 @@ def PwelchBatch(rows, Fs: float, o: Optional[PwelchOptions]):
                                   _p(win_seg), _p(win_nfft), int(not scaling), _p(pxx),
                                   _p(freqs), lpo), "PwelchBatch")
     return pxx, freqs
+
+
+class CrossSpectra(NamedTuple):
+    """What CpsdBatch / device.cpsd_batch return: row c of Pxy, Pxx, Pyy and
+    Cxy belongs to x row c against its y."""
+    Pxy: Any
+    Pxx: Any
+    Pyy: Any
+    Cxy: Any
+    freqs: Any
+
+
+def cpsd_batch_fused(channels: int, n: int, nfft: int = 0, pad: int = 0,
+                     noverlap: int = 0) -> bool:
+    """Whether cross spectra of this shape run the fused kernel over all
+    channels (True) or the materialised form (gdsp_cpsd_batch_fused)."""
+    return bool(lib().gdsp_cpsd_batch_fused(int(channels), int(n), int(nfft), int(pad),
+                                            int(noverlap)))
+
+
+def _rows(rows):
+    """A (channels, n) float64 array of equal-length rows, or the ragged panic."""
+    if isinstance(rows, np.ndarray) and rows.ndim == 2:
+        return np.ascontiguousarray(rows, dtype=np.float64)
+    rs = [np.asarray(r, dtype=np.float64).reshape(-1) for r in rows]
+    if any(r.size != rs[0].size for r in rs):
+        raise Panic(_lib.GDSP_ERR_RAGGED, "ragged input array")
+    return np.ascontiguousarray(rs, dtype=np.float64).reshape(len(rs), rs[0].size if rs else 0)
+
+
+def CpsdBatch(x_rows, y, Fs: float, o: Optional[PwelchOptions]) -> CrossSpectra:
+    """Welch cross spectra of every row of `x_rows` (equal lengths n) against
+    y: one row of n for all, or an array of x_rows' shape, row by row
+    (gdsp_cpsd_batch). Options, segments, windows, scaling and freqs are
+    Pwelch's. With X_s, Y_s the windowed spectra of segment s,
+    Pxy = c_j sum_s conj(X_s) Y_s / nsegs / norm (complex; MATLAB cpsd's and
+    scipy.signal.csd's sign), Pxx and Pyy the same of |X_s|^2 and |Y_s|^2, so
+    Pxx row c equals Pwelch(x_rows[c], Fs, o), and Cxy = |Sxy|^2 / (Sxx Syy),
+    the magnitude-squared coherence (mscohere, scipy.signal.coherence). Cxy is
+    the plain quotient: NaN in a bin that holds no power. One transform carries
+    a segment of x and of y; y's is packed times a power of 2 chosen from that
+    segment's two levels and taken out again exactly, so a difference in level
+    between the signals costs neither of them digits (include/gdsp_fft.h)."""
+    x = _rows(x_rows)
+    channels, n = x.shape
+    try:
+        yy = np.ascontiguousarray(y, dtype=np.float64)
+    except ValueError:  # a ragged y
+        raise Panic(_lib.GDSP_ERR_UNEQUAL, "arrays not of equal size") from None
+    if yy.shape != (n,) and yy.shape != (channels, n):
+        raise Panic(_lib.GDSP_ERR_UNEQUAL, "arrays not of equal size")
+    if n == 0:  # pwelch.go:75-77, before the options are looked at
+        e = np.zeros((channels, 0))
+        return CrossSpectra(e.astype(np.complex128), e, e.copy(), e.copy(), np.zeros(0))
+    nfft, pad, noverlap, wf, scaling = resolve_options(o)
+    flen = max(pad, nfft)
+    win_seg = np.ascontiguousarray(wf(flen), dtype=np.float64)
+    win_nfft = np.ascontiguousarray(wf(nfft), dtype=np.float64)
+    lp = pad // 2 + 1
+    pxy = np.empty((channels, lp), np.complex128)
+    pxx, pyy, coh = (np.empty((channels, lp), np.float64) for _ in range(3))
+    freqs = np.empty(lp, np.float64)
+    lpo = _lib._I64(0)
+    check(lib().gdsp_cpsd_batch(_p(x), n, _p(yy), n, 1 if yy.ndim == 1 else channels, channels, n,
+                                float(Fs), nfft, pad, noverlap, _p(win_seg), _p(win_nfft),
+                                int(not scaling), _p(pxy), _p(pxx), _p(pyy), _p(coh), _p(freqs),
+                                lpo), "CpsdBatch")
+    return CrossSpectra(pxy, pxx, pyy, coh, freqs)
+
+
+def _one_pair(x, y):
+    x = np.asarray(x, dtype=np.float64).reshape(-1)
+    y = np.asarray(y, dtype=np.float64).reshape(-1)
+    if x.size != y.size:
+        raise Panic(_lib.GDSP_ERR_UNEQUAL, "arrays not of equal size")
+    return x.reshape(1, -1), y
+
+
+def Cpsd(x, y, Fs: float, o: Optional[PwelchOptions]):
+    """The Welch cross power spectral density of two signals of equal length
+    (MATLAB cpsd, scipy.signal.csd): CpsdBatch of one row. Returns (Pxy,
+    freqs); Cpsd(x, x) is Pwelch(x)."""
+    x, y = _one_pair(x, y)
+    r = CpsdBatch(x, y, Fs, o)
+    return r.Pxy[0], r.freqs
+
+
+def Coherence(x, y, Fs: float, o: Optional[PwelchOptions]):
+    """The magnitude-squared coherence |Pxy|^2 / (Pxx Pyy) of two signals of
+    equal length (MATLAB mscohere, scipy.signal.coherence). Returns (Cxy,
+    freqs); NaN in a bin that holds no power."""
+    x, y = _one_pair(x, y)
+    r = CpsdBatch(x, y, Fs, o)
+    return r.Cxy[0], r.freqs
 
 
 def finalize(acc: np.ndarray, nsegs: int, nfft: int, pad: int, win_nfft: np.ndarray, Fs: float,

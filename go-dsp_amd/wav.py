@@ -235,6 +235,31 @@ def PwelchChannels(w: Wav, frames: int, o, Fs: float = 0.0):
     return pxx.cpu().numpy(), freqs
 
 
+def CoherenceChannels(w: Wav, frames: int, o, ref: int = 0, Fs: float = 0.0):
+    """The magnitude-squared coherence of every channel of a multi-channel
+    file with channel `ref`: the next `frames` frames of w, decoded planar on
+    the GPU as for PwelchChannels and run through device.cpsd_batch. Returns
+    (Cxy[NumChannels, lp], freqs) as numpy arrays; row c equals
+    spectral.Coherence(channel c, channel ref, Fs, o) (row ref is 1 wherever
+    the channel holds power). Fs defaults to w.SampleRate."""
+    import torch
+
+    from . import device
+    spectral.resolve_options(o)
+    C = int(w.NumChannels)
+    if not 0 <= ref < C:
+        raise _lib.GDSPError(_lib.GDSP_ERR_INVALID, f"reference channel {ref} of {C}")
+    raw, _ = w._read_raw(frames * C)
+    if frames == 0:  # pwelch.go:75-77
+        return np.zeros((C, 0)), np.zeros(0)
+    fs = float(Fs or w.SampleRate)
+    dev = torch.device("cuda", torch.cuda.current_device())
+    rd = torch.frombuffer(bytearray(raw), dtype=torch.uint8).to(dev)
+    x = device_floats_planar(rd, frames, C, w.AudioFormat, w.BitsPerSample)
+    r = device.cpsd_batch(x, x[ref], fs, o)
+    return r.Cxy.cpu().numpy(), r.freqs
+
+
 def Pwelch(w: Wav, n: int, o, Fs: float = 0.0):
     """The feeder end to end: the next n samples of w, decoded on the GPU
     into float64 and run through the device Pwelch (no host float pass);

@@ -103,7 +103,12 @@ enum {
   /* gdsp_pwelch_batch / gdsp_pwelch_batch_accumulate_device as a loop of
    * gdsp_pwelch_accumulate_device over the channels also for the lengths the
    * batched kernel serves. Read when the call is made. */
-  GDSP_ALGO_NO_FUSED_PWELCH_BATCH = 128
+  GDSP_ALGO_NO_FUSED_PWELCH_BATCH = 128,
+  /* gdsp_cpsd_batch / gdsp_cpsd_batch_accumulate_device on the materialised
+   * form (gathered rows, the plan's batched transform, a kernel over each row
+   * and its mirror) also for the lengths the fused cross-spectral kernel
+   * serves. Read when the call is made. */
+  GDSP_ALGO_NO_FUSED_CPSD = 256
 };
 /* Unknown bits → GDSP_ERR_INVALID (the selection is left unchanged). */
 int gdsp_set_algorithm(unsigned flags);
@@ -219,6 +224,54 @@ int gdsp_pwelch_batch(const double *x, int64_t channels, int64_t n, int64_t ldx,
  * arithmetic only (no GPU needed). */
 int gdsp_pwelch_batch_fused(int64_t channels, int64_t n, int64_t nfft, int64_t pad,
                             int64_t noverlap);
+
+/* Additive batched cross spectra (no reference equivalent; MATLAB cpsd /
+ * mscohere, scipy.signal.csd / coherence): `channels` signals x (channel c at
+ * x + c*ldx) each against y — y_rows == 1: one y (n float64) for all,
+ * y_rows == channels: channel c at y + c*ldy. Options, defaults, the
+ * zero-padding of a signal shorter than nfft, the segments, F = max(pad,
+ * nfft), the windows (NULL = Hann), norm, freqs and lp = pad/2+1 are
+ * gdsp_pwelch's. With X_s, Y_s the spectra gdsp_pwelch forms of segment s of
+ * x and y, Sxx[j] = sum_s |X_s[j]|^2, Syy[j] = sum_s |Y_s[j]|^2, Sxy[j] =
+ * sum_s conj(X_s[j]) Y_s[j] (MATLAB's and scipy's sign), and for j < lp
+ *   P..[j] = c_j S..[j] / nsegs / norm, c_j = 2 for 0 < j < lp-1, else 1
+ *   coh[j] = |Sxy[j]|^2 / (Sxx[j] Syy[j])
+ * so pxx of (x, x) is gdsp_pwelch's. The coherence is the plain IEEE
+ * quotient: a bin without power (and every bin when there is no segment)
+ * gives NaN. Without segments every P is 0.
+ * Accuracy: one transform carries a segment of x and the same segment of y
+ * (z = w x_s + i a w y_s), so its roundoff is relative to the larger of the two.
+ * a is a power of 2 chosen per segment from the binary exponents of
+ * max |w x_s| and max |w y_s| and taken out of that segment's products again,
+ * exactly: it evens out a difference in level between the two signals,
+ * segment by segment, and depends on nothing but that segment. What is left is
+ * a difference in level within one segment's spectra: a bin where one signal is
+ * far below the other signal's largest bin carries roundoff relative to the
+ * latter.
+ * pxy: channels × lp complex128; pxx, pyy, coh: channels × lp float64, each
+ * may be NULL (skipped); freqs: lp float64.
+ * Before any device call: a NULL lp_out, x, y, pxy or freqs that is needed,
+ * channels < 0, n < 0, nfft < 0, pad < 0, ldx < n with channels > 1 or ldy < n
+ * with y_rows > 1 → GDSP_ERR_INVALID; y_rows neither 1 nor channels →
+ * GDSP_ERR_UNEQUAL; a zero stride → GDSP_ERR_DIVIDE_BY_ZERO. n == 0 →
+ * *lp_out = 0, GDSP_OK; channels == 0 → only freqs and *lp_out written.
+ * F a power of 2 from 64 to 2048 runs one fused kernel over all channels
+ * (gdsp_cpsd_batch_fused); every other length the materialised form. Runs on
+ * the current device. */
+int gdsp_cpsd_batch(const double *x, int64_t ldx, const double *y, int64_t ldy, int64_t y_rows,
+                    int64_t channels, int64_t n, double fs, int64_t nfft, int64_t pad,
+                    int64_t noverlap, const double *win_seg, const double *win_nfft,
+                    int scale_off, double *pxy, double *pxx, double *pyy, double *coh,
+                    double *freqs, int64_t *lp_out);
+/* 1: a gdsp_cpsd_batch / gdsp_cpsd_batch_accumulate_device call of this shape
+ * (0 = the defaults) runs the fused kernel under the current flags; 0: the
+ * materialised form (F < 64, F = 4096 and up, non-powers of 2, strides above
+ * 2^22, GDSP_ALGO_NO_FUSED_CPSD). Host arithmetic only (no GPU needed): no
+ * plan is looked at. None needs to be: the library builds a power of 2 up to
+ * 2^14 as the one-kernel plan the fused kernel takes its twiddles from under
+ * every other flag. */
+int gdsp_cpsd_batch_fused(int64_t channels, int64_t n, int64_t nfft, int64_t pad,
+                          int64_t noverlap);
 
 /* window.Hann — window/window.go:62-76, as a host table generator used by the
  * shim for the default window (L float64 written to out). */
@@ -427,6 +480,37 @@ int gdsp_pwelch_batch_finalize_device(const double *d_acc, int64_t channels, int
                                       int64_t nsegs, int64_t nfft, int64_t pad,
                                       const double *win_nfft, double fs, int scale_off,
                                       double *d_pxx, double *freqs, void *stream);
+
+/* The cross-spectral sums of gdsp_cpsd_batch on device buffers: adds the
+ * sums over segments [seg_begin, seg_end) of every channel into d_acc,
+ * channels × 4 × hb float64 (hb = max(pad, nfft)/2 + 1; planes Sxx, Syy,
+ * Re Sxy, Im Sxy), zeroed by the caller before the first call. These are the
+ * true sums of the range (no pairing term is left in them, unlike the Pwelch
+ * accumulators), so ranges add in any split, and no segment's arithmetic
+ * depends on where a range begins (the balance of gdsp_cpsd_batch is per
+ * segment). d_x channel c at d_x + c*ldx,
+ * d_y at d_y + (y_rows == 1 ? 0 : c)*ldy; d_win_seg: the window of max(pad,
+ * nfft) on the device. nfft <= 0, pad <= 0, a negative or reversed range,
+ * channels < 0, n < 0, ldx < n with channels > 1, ldy < n with y_rows > 1, a
+ * needed NULL pointer, or seg_end past the signal → GDSP_ERR_INVALID; y_rows
+ * neither 1 nor channels → GDSP_ERR_UNEQUAL; nfft == noverlap with seg_end > 1
+ * → GDSP_ERR_DIVIDE_BY_ZERO; all before any device call. */
+int gdsp_cpsd_batch_accumulate_device(const double *d_x, int64_t ldx, const double *d_y,
+                                      int64_t ldy, int64_t y_rows, int64_t channels, int64_t n,
+                                      int64_t nfft, int64_t pad, int64_t noverlap,
+                                      int64_t seg_begin, int64_t seg_end,
+                                      const double *d_win_seg, double *d_acc, void *stream);
+
+/* Finalisation of d_acc (channels × 4 × (flen/2+1)) on the device into any of
+ * d_pxy (channels × lp complex128), d_pxx, d_pyy, d_coh (channels × lp
+ * float64), lp = pad/2+1; a NULL output is skipped. Every P by
+ * gdsp_pwelch_finalize's operations in its order. win_nfft: host table of
+ * nfft (NULL = Hann); freqs: host buffer of lp (may be NULL). */
+int gdsp_cpsd_batch_finalize_device(const double *d_acc, int64_t channels, int64_t flen,
+                                    int64_t nsegs, int64_t nfft, int64_t pad,
+                                    const double *win_nfft, double fs, int scale_off,
+                                    void *d_pxy, double *d_pxx, double *d_pyy, double *d_coh,
+                                    double *freqs, void *stream);
 
 /* gdsp_wav_read_floats_device for a multi-channel data chunk, into planar
  * float64 rows: d_out[c*ld_out + i] = the widened float32 of sample c of
