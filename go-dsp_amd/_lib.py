@@ -29,6 +29,9 @@ GDSP_ERR_HIP = 7
 GDSP_ERR_NOMEM = 8
 GDSP_ERR_UNSUPPORTED = 9
 
+# gdsp_set_algorithm: FIR filtering on the composed form (fft.ALGO_NO_FUSED_FIR)
+GDSP_ALGO_NO_FUSED_FIR = 512
+
 _P = ctypes.c_void_p
 _I64 = ctypes.c_int64
 _I = ctypes.c_int
@@ -51,6 +54,10 @@ SIGNATURES = {
     "gdsp_convolve_batch": (_I, [_P, _P, _P, _I64, _I64, _I64]),
     "gdsp_convolve_batch_device": (_I, [_P, _P, _P, _I64, _P, _I64, _P, _P]),
     "gdsp_convolve_fused": (_I, [_P]),
+    "gdsp_fir_block": (_I64, [_I64, _I64, ctypes.POINTER(_I)]),
+    "gdsp_fir_batch": (_I, [_P, _I64, _P, _I64, _I64, _I64, _I64, _I, _I64, _P, _I64]),
+    "gdsp_fir_batch_device": (_I, [_P, _I64, _P, _I64, _I64, _I64, _I64, _I, _I64, _P, _I64, _P,
+                                   _P]),
     "gdsp_fft_batch": (_I, [_P, _P, _I64, _I64, _I]),
     "gdsp_fft_real_batch": (_I, [_P, _P, _I64, _I64]),
     "gdsp_fft2": (_I, [_P, _P, _I64, _I64, _I]),

@@ -68,7 +68,7 @@ constexpr unsigned kAlgoAll = GDSP_ALGO_GENERIC_MIXED | GDSP_ALGO_NO_CHIRPZ_PART
                               GDSP_ALGO_CHIRPZ_POW2 | GDSP_ALGO_CHIRPZ_UNFUSED |
                               GDSP_ALGO_NO_RADER | GDSP_ALGO_NO_RACE |
                               GDSP_ALGO_NO_FUSED_CONVOLVE | GDSP_ALGO_NO_FUSED_PWELCH_BATCH |
-                              GDSP_ALGO_NO_FUSED_CPSD;
+                              GDSP_ALGO_NO_FUSED_CPSD | GDSP_ALGO_NO_FUSED_FIR;
 
 // Scratch device memory: a grow-only buffer per (device, stream, use-site
 // slot), allocated with hipMalloc. Reuse is ordered by the stream itself: a
@@ -83,6 +83,7 @@ enum Slot {
   SLOT_IN = 0, SLOT_OUT, SLOT_AUX, SLOT_AUX2, SLOT_GLOBAL, SLOT_GLOBAL_IN, SLOT_REAL,
   SLOT_BLU, SLOT_FFT2, SLOT_PW_PART, SLOT_PW_RED, SLOT_PW_BUF, SLOT_FS0, SLOT_FS1, SLOT_FS2,
   SLOT_FS3, SLOT_FFTN, SLOT_MX0, SLOT_MX1, SLOT_PARTS, SLOT_CONV, SLOT_CP_Y, SLOT_CP_OUT, SLOT_CP_BAL,
+  SLOT_FIR, SLOT_FIR_H, SLOT_FIR_OUT,
   SLOT_COUNT
 };
 
@@ -1015,6 +1016,224 @@ int gdsp_convolve_batch(const double *x, const double *y, double *out, int64_t n
     return st;
   }
   STCHK(copy_d2h(out, dx.p, xb, s));  // returns after the stream drained
+  return GDSP_OK;
+}
+
+// ---- FIR filtering of real rows by overlap-save (fir.hip) --------------------
+// The block length is host arithmetic on a committed table: per-F cost of the
+// fused kernel, ms per 2^27 points through its transform pair (time x L / F
+// per 2^27 samples), the median over the lines of that F in this kernel's own
+// sweep (scripts/bench_fir.py, the cost_table of profiles/fir_batch.json;
+// DESIGN.md §3). Nothing is timed when a call is made.
+static constexpr int kFirMinLog2 = gdsp::kConvMinLog2, kFirMaxLog2 = gdsp::kMaxLdsLog2;
+static constexpr int kFirComposedMaxLog2 = 20;
+static const double kFirCost[kFirMaxLog2 - kFirMinLog2 + 1] = {0.5123, 0.4192, 0.4006, 0.4420,
+                                                                0.4340, 0.4775, 0.6127};
+
+// The block length of a call (0: the call fails) and whether F and m alone
+// admit the fused kernel
+static int64_t fir_block_for(int64_t m, int64_t block, bool *fused_range) {
+  *fused_range = false;
+  if (m <= 0 || block < 0) return 0;
+  int64_t F = 0;
+  if (block != 0) {
+    if (!gdsp_api::is_pow2(block) || block < ((int64_t)1 << kFirMinLog2) ||
+        block > ((int64_t)1 << kFirComposedMaxLog2) || block < 2 * m)
+      return 0;
+    F = block;
+  } else if (m <= ((int64_t)1 << (kFirMaxLog2 - 1))) {
+    double best = 0;
+    for (int k = kFirMinLog2; k <= kFirMaxLog2; ++k) {
+      const int64_t f = (int64_t)1 << k;
+      if (f < 2 * m) continue;
+      const double c = kFirCost[k - kFirMinLog2] * (double)f / (double)(f - m + 1);
+      if (F == 0 || c < best) {
+        F = f;
+        best = c;
+      }
+    }
+  } else {
+    // beyond the fused kernel: the smallest power of 2 that is at least 4
+    // times the halo of m - 1 samples (8193 taps run on 32768)
+    F = (int64_t)1 << kFirComposedMaxLog2;
+    if (4 * (m - 1) > F) return 0;
+    while (F / 2 >= 4 * (m - 1)) F /= 2;
+  }
+  *fused_range = F <= ((int64_t)1 << kFirMaxLog2) && 2 * m <= F;
+  return F;
+}
+
+// transforms per row and in all: two blocks of L = F - m + 1 outputs each
+static void fir_geometry(int64_t F, int64_t m, int64_t channels, int64_t out_len, int64_t *tpr,
+                         int64_t *total) {
+  const int64_t L = F - m + 1, nb = (out_len + L - 1) / L;
+  *tpr = (nb + 1) / 2;
+  *total = channels * *tpr;
+}
+
+static bool fir_fused(int64_t F, bool fused_range, int64_t total) {
+  return fused_range && !(g_algo.load() & GDSP_ALGO_NO_FUSED_FIR) &&
+         gdsp::fir_ols_workgroups(gdsp_api::ilog2(F), total) <= 0x7fffffff;
+}
+
+// rows of the composed form's chunk: at most 256 MiB of complex rows
+static int64_t fir_chunk_rows(int64_t F, int64_t total) {
+  int64_t r = ((int64_t)1 << 24) / F;
+  if (r < 1) r = 1;
+  return r < total ? r : total;
+}
+
+// Argument checks shared by the host and device entries, in the order of the
+// header's table; *done: nothing to do. No device call is made.
+static int fir_check(const void *x, int64_t ldx, const void *h, int64_t h_rows, int64_t m,
+                     int64_t channels, int64_t n, int full, int64_t block, const void *out,
+                     int64_t ldo, int64_t *F, bool *fused_range, bool *done) {
+  *done = false;
+  *F = 0;
+  if (m < 0 || n < 0 || channels < 0 || h_rows < 0 || block < 0)
+    return fail(GDSP_ERR_INVALID, "negative size");
+  if (full != 0 && full != 1) return fail(GDSP_ERR_INVALID, "full must be 0 or 1");
+  if (h_rows != 1 && h_rows != channels)
+    return fail(GDSP_ERR_INVALID, "h_rows must be 1 or the channels");
+  if (block != 0 && (!gdsp_api::is_pow2(block) || block < ((int64_t)1 << kFirMinLog2) ||
+                     block > ((int64_t)1 << kFirComposedMaxLog2) || block < 2 * m))
+    return fail(GDSP_ERR_INVALID, "block must be a power of 2 in [256, 2^20] and at least 2 m");
+  if (n > INT64_MAX / 4 || m > INT64_MAX / 4) return fail(GDSP_ERR_INVALID, "size overflow");
+  const int64_t out_len = full ? n + m - 1 : n;
+  if (channels > 1 && (ldx < n || ldo < out_len))
+    return fail(GDSP_ERR_INVALID, "row stride below the row length");
+  if (channels == 0) {
+    *done = true;
+    return GDSP_OK;
+  }
+  if (n == 0 || m == 0) return fail(GDSP_ERR_EMPTY, "empty input array");
+  *F = fir_block_for(m, block, fused_range);
+  if (*F == 0) return fail(GDSP_ERR_UNSUPPORTED, "taps beyond the composed form's block lengths");
+  if (!x || !h || !out) return fail(GDSP_ERR_INVALID, "NULL pointer");
+  return GDSP_OK;
+}
+
+// d_work: h_rows F complex128 (the taps' spectra), then in the composed form
+// fir_chunk_rows(F, total) rows of F more
+static int fir_rows(const double *d_x, int64_t ldx, const double *d_h, int64_t h_rows, int64_t m,
+                    int64_t channels, int64_t n, int64_t out_len, int64_t F, bool fused_range,
+                    double *d_out, int64_t ldo, cd *work, hipStream_t s) {
+  gdsp_plan *p = nullptr;
+  STCHK(get_plan(F, &p));
+  int64_t tpr = 0, total = 0;
+  fir_geometry(F, m, channels, out_len, &tpr, &total);
+  const int64_t hstride = h_rows == 1 ? 0 : F;
+  HIPCHK(gdsp::launch_fir_taps(d_h, h_rows, m, F, work, s));
+  STCHK(exec_plan(p, work, work, h_rows, false, gdsp::LOAD_COMPLEX, s));
+  // get_plan builds a power of 2 up to 2^14 as KIND_LDS under every flag set
+  // (build_plan, plan.hip); the kind is checked because the kernel reads that
+  // plan's twiddle table
+  if (fir_fused(F, fused_range, total) && p->kind == KIND_LDS) {
+    HIPCHK(gdsp::launch_fir_ols(p->log2n, d_x, ldx, d_out, ldo, channels, n, out_len, m, p->tw,
+                                work, hstride, s));
+    return GDSP_OK;
+  }
+  cd *buf = work + h_rows * F;
+  const int64_t rows = fir_chunk_rows(F, total);
+  for (int64_t g0 = 0; g0 < total; g0 += rows) {
+    const int64_t cnt = total - g0 < rows ? total - g0 : rows;
+    HIPCHK(gdsp::launch_fir_gather(d_x, ldx, g0, cnt, tpr, n, m, F, buf, s));
+    STCHK(exec_plan(p, buf, buf, cnt, false, gdsp::LOAD_COMPLEX, s));
+    if (h_rows == 1) {
+      HIPCHK(gdsp::launch_pointwise_mul_rows(buf, work, 0, buf, F, cnt, s));
+    } else {
+      // one multiply per channel's run of rows in the chunk
+      for (int64_t g = g0; g < g0 + cnt;) {
+        const int64_t c = g / tpr, end = (c + 1) * tpr < g0 + cnt ? (c + 1) * tpr : g0 + cnt;
+        cd *run = buf + (g - g0) * F;
+        HIPCHK(gdsp::launch_pointwise_mul_rows(run, work + c * F, 0, run, F, end - g, s));
+        g = end;
+      }
+    }
+    STCHK(exec_plan(p, buf, buf, cnt, true, gdsp::LOAD_COMPLEX, s));
+    HIPCHK(gdsp::launch_fir_scatter(buf, g0, cnt, tpr, out_len, m, F, d_out, ldo, s));
+  }
+  return GDSP_OK;
+}
+
+static size_t fir_work_bytes(int64_t F, int64_t m, int64_t h_rows, int64_t channels,
+                             int64_t out_len, bool fused_range) {
+  int64_t tpr = 0, total = 0;
+  fir_geometry(F, m, channels, out_len, &tpr, &total);
+  const int64_t rows = h_rows + (fir_fused(F, fused_range, total) ? 0 : fir_chunk_rows(F, total));
+  return (size_t)rows * (size_t)F * sizeof(cd);
+}
+
+int64_t gdsp_fir_block(int64_t m, int64_t block, int *fused) {
+  bool fr = false;
+  const int64_t F = fir_block_for(m, block, &fr);
+  if (fused) *fused = F != 0 && fr && !(g_algo.load() & GDSP_ALGO_NO_FUSED_FIR) ? 1 : 0;
+  return F;
+}
+
+int gdsp_fir_batch_device(const void *d_x, int64_t ldx, const void *d_h, int64_t h_rows,
+                          int64_t m, int64_t channels, int64_t n, int full, int64_t block,
+                          void *d_out, int64_t ldo, void *d_work, void *stream) {
+  int64_t F = 0;
+  bool fr = false, done = false;
+  STCHK(fir_check(d_x, ldx, d_h, h_rows, m, channels, n, full, block, d_out, ldo, &F, &fr, &done));
+  if (done) return GDSP_OK;
+  const int64_t out_len = full ? n + m - 1 : n;
+  // a block's halo is another workgroup's output range: no overlap at all
+  const uintptr_t xa = (uintptr_t)d_x, oa = (uintptr_t)d_out;
+  const uintptr_t xe = xa + ((uintptr_t)(channels - 1) * (uintptr_t)ldx + (uintptr_t)n) * 8;
+  const uintptr_t oe = oa + ((uintptr_t)(channels - 1) * (uintptr_t)ldo + (uintptr_t)out_len) * 8;
+  if (xa < oe && oa < xe) return fail(GDSP_ERR_INVALID, "d_out overlaps d_x");
+  hipStream_t s = (hipStream_t)stream;
+  DevBuf w;
+  cd *work = (cd *)d_work;
+  if (!work) {
+    STCHK(w.alloc(fir_work_bytes(F, m, h_rows, channels, out_len, fr), s, SLOT_FIR));
+    work = (cd *)w.p;
+  }
+  return fir_rows((const double *)d_x, channels > 1 ? ldx : n, (const double *)d_h, h_rows, m,
+                  channels, n, out_len, F, fr, (double *)d_out, channels > 1 ? ldo : out_len, work,
+                  s);
+}
+
+int gdsp_fir_batch(const double *x, int64_t ldx, const double *h, int64_t h_rows, int64_t m,
+                   int64_t channels, int64_t n, int full, int64_t block, double *out,
+                   int64_t ldo) {
+  int64_t F = 0;
+  bool fr = false, done = false;
+  STCHK(fir_check(x, ldx, h, h_rows, m, channels, n, full, block, out, ldo, &F, &fr, &done));
+  if (done) return GDSP_OK;
+  const int64_t out_len = full ? n + m - 1 : n;
+  int dev = 0;
+  STCHK(current_device(&dev));
+  hipStream_t s = thread_stream(dev);
+  if (!s) return fail(GDSP_ERR_HIP, "stream creation failed");
+  const size_t xrow = (size_t)n * sizeof(double), orow = (size_t)out_len * sizeof(double);
+  DevBuf dx, dh, dout, dw;
+  STCHK(dx.alloc((size_t)channels * xrow, s, SLOT_IN));
+  STCHK(dh.alloc((size_t)h_rows * (size_t)m * sizeof(double), s, SLOT_FIR_H));
+  STCHK(dout.alloc((size_t)channels * orow, s, SLOT_FIR_OUT));
+  STCHK(dw.alloc(fir_work_bytes(F, m, h_rows, channels, out_len, fr), s, SLOT_FIR));
+  double *px = (double *)dx.p, *po = (double *)dout.p;
+  auto queue = [&]() -> int {
+    if (channels == 1 || ldx == n) {
+      STCHK(copy_h2d(px, x, (size_t)channels * xrow, s));
+    } else {
+      for (int64_t c = 0; c < channels; ++c) STCHK(copy_h2d(px + c * n, x + c * ldx, xrow, s));
+    }
+    STCHK(copy_h2d(dh.p, h, (size_t)h_rows * (size_t)m * sizeof(double), s));
+    return fir_rows(px, n, (const double *)dh.p, h_rows, m, channels, n, out_len, F, fr, po,
+                    out_len, (cd *)dw.p, s);
+  };
+  const int st = queue();
+  if (st != GDSP_OK) {
+    (void)hipStreamSynchronize(s);  // queued copies still read the staging halves
+    return st;
+  }
+  // every sample left the caller's memory before the first result lands in
+  // it, so out may alias x
+  if (channels == 1 || ldo == out_len) return copy_d2h(out, po, (size_t)channels * orow, s);
+  for (int64_t c = 0; c < channels; ++c) STCHK(copy_d2h(out + c * ldo, po + c * out_len, orow, s));
   return GDSP_OK;
 }
 

@@ -282,6 +282,26 @@ hipError_t launch_convolve_lds(int log2n, const cd *x, cd *out, int64_t batch, c
 // out[g n + k] = a[g n + k] * b[g b_stride + k] (b_stride 0 or n); out may alias a
 hipError_t launch_pointwise_mul_rows(const cd *a, const cd *b, int64_t b_stride, cd *out,
                                      int64_t n, int64_t batch, hipStream_t s);
+// Overlap-save FIR filter of real rows (fir.hip): out[c ldo + i] = sum_{k<m}
+// h[k] x[c ldx + i - k] for i < out_len (n, or n + m - 1), x zero outside
+// [0, n). Blocks of L = F - m + 1 outputs, two per transform, tpr =
+// ceil(ceil(out_len / L) / 2) transforms per row. hspec = FFT_F of the
+// zero-padded taps (launch_fir_taps, then the plan's transform), hstride 0
+// (one for all rows) or F. The fused kernel: F = 2^log2f, 2^kConvMinLog2 ...
+// 2^kMaxLdsLog2, m <= F / 2, in fir_ols_workgroups(log2f, channels * tpr)
+// workgroups; out must not overlap x. The composed form's ends for any F >=
+// m: transforms [g0, g0 + cnt) of the job gathered as complex rows of F, and
+// the valid parts of their inverse transforms scattered.
+int64_t fir_ols_workgroups(int log2f, int64_t total);
+hipError_t launch_fir_ols(int log2f, const double *x, int64_t ldx, double *out, int64_t ldo,
+                          int64_t channels, int64_t n, int64_t out_len, int64_t m, const cd *tw,
+                          const cd *hspec, int64_t hstride, hipStream_t s);
+hipError_t launch_fir_taps(const double *h, int64_t h_rows, int64_t m, int64_t F, cd *out,
+                           hipStream_t s);
+hipError_t launch_fir_gather(const double *x, int64_t ldx, int64_t g0, int64_t cnt, int64_t tpr,
+                             int64_t n, int64_t m, int64_t F, cd *buf, hipStream_t s);
+hipError_t launch_fir_scatter(const cd *buf, int64_t g0, int64_t cnt, int64_t tpr, int64_t out_len,
+                              int64_t m, int64_t F, double *out, int64_t ldo, hipStream_t s);
 // wav.ReadFloats conversion (wav.hip): audio_format 1 (bits 8 / 16) or 3
 hipError_t launch_wav_decode(const void *in, int64_t count, int audio_format, int bits,
                              void *out, bool f64, hipStream_t s);

@@ -123,6 +123,41 @@ def convolve_batch(x, y, out=None, work=None, stream=None):
     return out
 
 
+def fir_batch(x, h, out=None, full: bool = False, block: int = 0, work=None, stream=None):
+    """fft.FIRFilterBatch on float64 CUDA tensors: every row of x (channels,
+    n; unit inner stride, any row stride) filtered with the taps h, (m,) or
+    (channels, m) contiguous, into out (channels, n, or n + m - 1 with
+    full=True; unit inner stride, any row stride), which must not overlap x.
+    block: the overlap-save block length (0: fft.fir_block's choice). work:
+    scratch (complex128) as gdsp_fir_batch_device sizes it; with it the fused
+    form does not allocate (gdsp_fir_batch_device)."""
+    torch = _torch()
+    assert x.is_cuda and x.dtype == torch.float64 and x.dim() == 2
+    assert h.is_cuda and h.dtype == torch.float64 and h.device == x.device and h.is_contiguous()
+    channels, n = x.shape
+    if h.dim() not in (1, 2) or (h.dim() == 2 and h.shape[0] != channels):
+        raise _lib.Panic(_lib.GDSP_ERR_UNEQUAL, "arrays not of equal size")
+    m = h.shape[-1]
+    out_len = n + m - 1 if full else n
+    if out is None:
+        out = torch.empty((channels, max(out_len, 0)), dtype=torch.float64, device=x.device)
+    assert out.is_cuda and out.dtype == torch.float64 and out.device == x.device
+    assert tuple(out.shape) == (channels, max(out_len, 0))
+    assert n == 0 or x.stride(1) == 1, "rows must have unit inner stride"
+    assert out_len <= 0 or out.stride(1) == 1, "rows must have unit inner stride"
+    ldx = x.stride(0) if channels > 1 else n
+    ldo = out.stride(0) if channels > 1 else out_len
+    if work is not None:
+        assert work.is_cuda and work.dtype == torch.complex128 and work.is_contiguous()
+    h_rows = 1 if h.dim() == 1 else channels
+    with torch.cuda.device(x.device):
+        wp = _ptr(work) if work is not None else ctypes.c_void_p()
+        check(lib().gdsp_fir_batch_device(_ptr(x), ldx, _ptr(h), h_rows, m, channels, n,
+                                          int(bool(full)), int(block), _ptr(out), ldo, wp,
+                                          _stream_ptr(stream, x.device)), "fir_batch_device")
+    return out
+
+
 def fft_real_batch(x, out=None, inverse: bool = False, stream=None, chirpz: bool = False):
     """fft.FFTReal / IFFTReal of the rows of a (batch, n) float64 CUDA tensor
     into a complex128 tensor (gdsp_fft_real_batch_device: the kernels read the

@@ -87,6 +87,76 @@ def ConvolveBatch(x, y) -> np.ndarray:
     return out
 
 
+def _real_rows(x, what: str) -> np.ndarray:
+    """A list of real rows as a (channels, n) float64 array: ragged rows
+    panic, complex samples are refused (never cast)."""
+    if not isinstance(x, np.ndarray):
+        rows = [np.asarray(r) for r in x]
+        if any(r.ndim != 1 or r.size != rows[0].size for r in rows):
+            raise Panic(_lib.GDSP_ERR_RAGGED, "ragged input array")
+        if any(np.iscomplexobj(r) for r in rows):
+            raise TypeError(f"{what}: complex input is not supported")
+        x = np.asarray(rows, dtype=np.float64).reshape(len(rows), rows[0].size if rows else 0)
+    if np.iscomplexobj(x):
+        raise TypeError(f"{what}: complex input is not supported")
+    x = np.asarray(x, dtype=np.float64)
+    if x.ndim != 2:
+        raise ValueError(f"{what} expects a 2-D (channels, n) array")
+    return np.ascontiguousarray(x)
+
+
+def fir_block(m: int, block: int = 0) -> tuple[int, bool]:
+    """(F, fused): the overlap-save block length FIRFilterBatch uses for m taps
+    (block=0: the library's choice; F = 0 where the call would fail) and
+    whether the fused kernel runs it under the current algorithm flags
+    (gdsp_fir_block; host arithmetic)."""
+    fused = _lib._I(0)
+    f = int(lib().gdsp_fir_block(int(m), int(block), fused))
+    return f, bool(fused.value)
+
+
+def FIRFilterBatch(rows, h, full: bool = False, block: int = 0) -> np.ndarray:
+    """Additive FIR filter of every row of the real (channels, n) array (or
+    list of rows) with the real taps h — (m,): one filter for all rows, or
+    (channels, m): row by row: out[c, i] = sum_k h[k] rows[c, i - k], rows
+    taken as zero outside [0, n). full=False: n samples per row
+    (scipy.signal.lfilter(h, 1, x)); full=True: n + m - 1 (numpy.convolve).
+    block: the overlap-save block length (0: the library's choice)."""
+    x = _real_rows(rows, "FIRFilterBatch")
+    if np.iscomplexobj(h):
+        raise TypeError("FIRFilterBatch: complex taps are not supported")
+    h = np.asarray(h, dtype=np.float64)  # (ascontiguousarray would make a scalar 1-D)
+    channels, n = x.shape
+    if h.ndim == 0 or h.ndim > 2 or (h.ndim == 2 and h.shape[0] != channels):
+        raise Panic(_lib.GDSP_ERR_UNEQUAL, "arrays not of equal size")
+    h = np.ascontiguousarray(h)
+    m = h.shape[-1]
+    out_len = n + m - 1 if full else n
+    out = np.empty((channels, max(out_len, 0)), np.float64)
+    if channels == 0:
+        return out
+    h_rows = 1 if h.ndim == 1 else channels
+    check(lib().gdsp_fir_batch(_p(x), n, _p(h), h_rows, m, channels, n, int(bool(full)),
+                               int(block), _p(out), out_len), "FIRFilterBatch")
+    return out
+
+
+def FIRFilter(x, h) -> np.ndarray:
+    """The causal FIR filter of the real signal x with the real taps h: n
+    samples, scipy.signal.lfilter(h, 1, x) (FIRFilterBatch of one row)."""
+    if np.iscomplexobj(x):
+        raise TypeError("FIRFilter: complex input is not supported")
+    return FIRFilterBatch(np.asarray(x, dtype=np.float64).reshape(1, -1), h)[0]
+
+
+def ConvolveLinear(x, h) -> np.ndarray:
+    """The linear convolution of the real vectors x and h: n + m - 1 samples,
+    numpy.convolve(x, h) (FIRFilterBatch of one row, full)."""
+    if np.iscomplexobj(x):
+        raise TypeError("ConvolveLinear: complex input is not supported")
+    return FIRFilterBatch(np.asarray(x, dtype=np.float64).reshape(1, -1), h, full=True)[0]
+
+
 def FFTBatch(x, inverse: bool = False) -> np.ndarray:
     """Additive batched entry point: FFT (or IFFT) of every row
     of a (batch, n) complex array, in one GPU launch."""
@@ -228,6 +298,7 @@ ALGO_NO_RACE = 32
 ALGO_NO_FUSED_CONVOLVE = 64
 ALGO_NO_FUSED_PWELCH_BATCH = 128
 ALGO_NO_FUSED_CPSD = 256
+ALGO_NO_FUSED_FIR = _lib.GDSP_ALGO_NO_FUSED_FIR
 
 
 def SetAlgorithm(flags: int = ALGO_DEFAULT) -> None:

@@ -260,6 +260,31 @@ def CoherenceChannels(w: Wav, frames: int, o, ref: int = 0, Fs: float = 0.0):
     return r.Cxy.cpu().numpy(), r.freqs
 
 
+def FilterChannels(w: Wav, frames: int, h, full: bool = False):
+    """Every channel of a multi-channel file through a FIR filter: the next
+    `frames` frames of w, decoded planar on the GPU as for PwelchChannels and
+    run through device.fir_batch with the real taps h ((m,): one filter for
+    all channels, or (NumChannels, m)). Returns a (NumChannels, out_len)
+    numpy array, out_len = frames, or frames + m - 1 with full=True; row c
+    equals fft.FIRFilterBatch of channel c's decoded samples."""
+    import torch
+
+    from . import device
+    if np.iscomplexobj(h):
+        raise TypeError("FilterChannels: complex taps are not supported")
+    h = np.asarray(h, dtype=np.float64)
+    C = int(w.NumChannels)
+    if h.ndim not in (1, 2) or (h.ndim == 2 and h.shape[0] != C):
+        raise _lib.Panic(_lib.GDSP_ERR_UNEQUAL, "arrays not of equal size")
+    h = np.ascontiguousarray(h)
+    raw, _ = w._read_raw(frames * C)
+    dev = torch.device("cuda", torch.cuda.current_device())
+    rd = torch.frombuffer(bytearray(raw), dtype=torch.uint8).to(dev)
+    x = device_floats_planar(rd, frames, C, w.AudioFormat, w.BitsPerSample)
+    out = device.fir_batch(x, torch.from_numpy(h).to(dev), full=full)
+    return out.cpu().numpy()
+
+
 def Pwelch(w: Wav, n: int, o, Fs: float = 0.0):
     """The feeder end to end: the next n samples of w, decoded on the GPU
     into float64 and run through the device Pwelch (no host float pass);

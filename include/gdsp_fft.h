@@ -108,7 +108,12 @@ enum {
    * form (gathered rows, the plan's batched transform, a kernel over each row
    * and its mirror) also for the lengths the fused cross-spectral kernel
    * serves. Read when the call is made. */
-  GDSP_ALGO_NO_FUSED_CPSD = 256
+  GDSP_ALGO_NO_FUSED_CPSD = 256,
+  /* gdsp_fir_batch / gdsp_fir_batch_device on the composed form (gathered
+   * blocks, the plan's batched transform, row multiply, inverse transform,
+   * scatter of the valid parts) also for the block lengths the fused
+   * overlap-save kernel serves. Read when the call is made. */
+  GDSP_ALGO_NO_FUSED_FIR = 512
 };
 /* Unknown bits → GDSP_ERR_INVALID (the selection is left unchanged). */
 int gdsp_set_algorithm(unsigned flags);
@@ -147,6 +152,42 @@ int gdsp_convolve(const double *x, const double *y, double *out, int64_t n);
  * device. */
 int gdsp_convolve_batch(const double *x, const double *y, double *out,
                         int64_t n, int64_t batch, int64_t y_rows);
+
+/* Additive FIR filtering of real rows (no reference equivalent; the causal
+ * filter of scipy.signal.lfilter(h, 1, x), or numpy.convolve(x, h)): for
+ * `channels` rows of n float64, row c at x + c*ldx, and m real taps,
+ *   out[c*ldo + i] = sum over k < m of h[k] * x[c*ldx + i - k],
+ * x taken as zero outside [0, n); i in [0, n) with full == 0, in
+ * [0, n + m - 1) with full == 1 (the tail lets a caller overlap-add the
+ * chunks of a stream). h_rows == 1 → one h for all rows, h_rows == channels →
+ * row c takes h + c*m. Strides in doubles. Computed by overlap-save on blocks
+ * of F = gdsp_fir_block(m, block) points: where that reports `fused`, one
+ * kernel per call after the spectrum of the taps (two overlapping blocks of a
+ * row per transform as a + i b, FFT_F, times FFT_F(h), inverse FFT_F, the valid
+ * parts of Re and Im stored: the samples are read about once and written
+ * once); otherwise the composed form in chunks of at most 256 MiB of blocks.
+ * out may alias x: the caller's memory is only touched by host memcpy.
+ * In this order, before any device call: a negative size, full not 0 or 1,
+ * h_rows neither 1 nor channels, a block that gdsp_fir_block rejects for
+ * another reason than m's range, ldx < n or ldo < the output length with
+ * channels > 1 → GDSP_ERR_INVALID; channels == 0 → GDSP_OK, nothing done;
+ * n == 0 or m == 0 → GDSP_ERR_EMPTY (as numpy.convolve refuses empty input);
+ * m beyond the composed form's range → GDSP_ERR_UNSUPPORTED; a NULL pointer →
+ * GDSP_ERR_INVALID. Runs on the current device. */
+int gdsp_fir_batch(const double *x, int64_t ldx, const double *h, int64_t h_rows, int64_t m,
+                   int64_t channels, int64_t n, int full, int64_t block, double *out,
+                   int64_t ldo);
+
+/* The overlap-save block length F of a gdsp_fir_batch call with m taps (no
+ * reference equivalent), or 0 where that call would fail; host arithmetic on
+ * a committed cost table, the same answer every time, no GPU needed. block: a
+ * power of 2, 256 <= block <= 2^20, block >= 2m, is taken as it is; 0 → the
+ * library's choice: for m <= 8192 the F in {256 ... 16384}, F >= 2m, of least
+ * cost(F) * F / (F - m + 1); above, the smallest power of 2 >= 4 (m - 1), up
+ * to 2^20. *fused (may be NULL): 1 where the fused kernel serves F and m
+ * (256 <= F <= 16384, m <= F/2) under the current flags (a call whose grid
+ * would pass 2^31 - 1 workgroups still runs composed). */
+int64_t gdsp_fir_block(int64_t m, int64_t block, int *fused);
 
 /* Additive batched entry point (no reference equivalent): the
  * same transform as fft.FFT / fft.IFFT applied to `batch` contiguous rows of n
@@ -422,6 +463,19 @@ int gdsp_convolve_batch_device(const gdsp_plan *plan, const void *d_x, const voi
                                void *d_work, void *stream);
 /* 1: the fused kernel serves this plan under the current flags; 0: composed */
 int gdsp_convolve_fused(const gdsp_plan *plan);
+
+/* gdsp_fir_batch on device buffers (no reference equivalent), stream-ordered:
+ * d_x rows of n float64 at stride ldx, d_h h_rows*m float64, d_out rows of
+ * the output length at stride ldo. The address ranges of d_x and d_out must
+ * not overlap (a block reads a halo that another workgroup writes):
+ * GDSP_ERR_INVALID. d_work: scratch (may be NULL: the library's workspace
+ * pool) of 16*F*h_rows bytes for the taps' spectra, and in the composed form
+ * 16*F*min(T, max(1, 2^24 / F)) more, T = channels * ceil(ceil(output length /
+ * (F - m + 1)) / 2) transforms. Status codes as gdsp_fir_batch, decided
+ * before any device call. */
+int gdsp_fir_batch_device(const void *d_x, int64_t ldx, const void *d_h, int64_t h_rows,
+                          int64_t m, int64_t channels, int64_t n, int full, int64_t block,
+                          void *d_out, int64_t ldo, void *d_work, void *stream);
 
 /* FFT2/IFFT2 on a device rows×cols complex128 matrix. d_work: scratch of
  * rows*cols complex128 (may be NULL: the library allocates stream-ordered). */
