@@ -1,7 +1,9 @@
 // gdsp_api.hip — the C ABI of libgdspfft (include/gdsp_fft.h): per-thread
 // streams, staging and workspaces, the executors of a plan (plan.hip builds
 // it), host-pointer entry points (what cgo binds) and device-pointer entry
-// points (what the multi-GPU drivers call).
+// points (what the multi-GPU drivers call). The Welch family's entries
+// (Pwelch, batched Pwelch, Cpsd) are in welch.hip; api_internal.hpp is what
+// the two share.
 //
 // Every transform runs on the GPU. There is no CPU compute path: without a
 // HIP device the entry points return GDSP_ERR_NO_DEVICE.
@@ -79,14 +81,6 @@ constexpr unsigned kAlgoAll = GDSP_ALGO_GENERIC_MIXED | GDSP_ALGO_NO_CHIRPZ_PART
 // intermittently under the ROCm 7.2 runtime here — tests/cpp reproduced it —
 // so the library does not use it.) Device-API callers must not drive one
 // stream from two host threads at once.
-enum Slot {
-  SLOT_IN = 0, SLOT_OUT, SLOT_AUX, SLOT_AUX2, SLOT_GLOBAL, SLOT_GLOBAL_IN, SLOT_REAL,
-  SLOT_BLU, SLOT_FFT2, SLOT_PW_PART, SLOT_PW_RED, SLOT_PW_BUF, SLOT_FS0, SLOT_FS1, SLOT_FS2,
-  SLOT_FS3, SLOT_FFTN, SLOT_MX0, SLOT_MX1, SLOT_PARTS, SLOT_CONV, SLOT_CP_Y, SLOT_CP_OUT, SLOT_CP_BAL,
-  SLOT_FIR, SLOT_FIR_H, SLOT_FIR_OUT,
-  SLOT_COUNT
-};
-
 struct Workspace {
   void *buf[SLOT_COUNT] = {};
   size_t cap[SLOT_COUNT] = {};
@@ -95,35 +89,34 @@ struct Workspace {
 std::mutex g_ws_mu;
 std::map<std::pair<int, hipStream_t>, Workspace> g_ws;
 
-struct DevBuf {
-  void *p = nullptr;
-  DevBuf() = default;
-  DevBuf(const DevBuf &) = delete;
-  int alloc(size_t bytes, hipStream_t st, Slot slot) {
-    if (bytes == 0) bytes = 16;
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess) return fail(GDSP_ERR_NO_DEVICE, "hipGetDevice failed");
-    std::lock_guard<std::mutex> lk(g_ws_mu);
-    Workspace &w = g_ws[std::make_pair(dev, st)];
-    if (w.cap[slot] < bytes) {
-      if (w.buf[slot]) {
-        HIPCHK(hipStreamSynchronize(st));  // queued users of the old buffer
-        HIPCHK(hipFree(w.buf[slot]));
-        w.buf[slot] = nullptr;
-        w.cap[slot] = 0;
-      }
-      const size_t want = bytes + bytes / 4;  // headroom against regrowth
-      hipError_t e = hipMalloc(&w.buf[slot], want);
-      if (e != hipSuccess) {
-        w.buf[slot] = nullptr;
-        return fail(GDSP_ERR_NOMEM, std::string("hipMalloc: ") + hipGetErrorString(e));
-      }
-      w.cap[slot] = want;
+}  // namespace
+
+int gdsp_api::DevBuf::alloc(size_t bytes, hipStream_t st, Slot slot) {
+  if (bytes == 0) bytes = 16;
+  int dev = 0;
+  if (hipGetDevice(&dev) != hipSuccess) return fail(GDSP_ERR_NO_DEVICE, "hipGetDevice failed");
+  std::lock_guard<std::mutex> lk(g_ws_mu);
+  Workspace &w = g_ws[std::make_pair(dev, st)];
+  if (w.cap[slot] < bytes) {
+    if (w.buf[slot]) {
+      HIPCHK(hipStreamSynchronize(st));  // queued users of the old buffer
+      HIPCHK(hipFree(w.buf[slot]));
+      w.buf[slot] = nullptr;
+      w.cap[slot] = 0;
     }
-    p = w.buf[slot];
-    return GDSP_OK;
+    const size_t want = bytes + bytes / 4;  // headroom against regrowth
+    hipError_t e = hipMalloc(&w.buf[slot], want);
+    if (e != hipSuccess) {
+      w.buf[slot] = nullptr;
+      return fail(GDSP_ERR_NOMEM, std::string("hipMalloc: ") + hipGetErrorString(e));
+    }
+    w.cap[slot] = want;
   }
-};
+  p = w.buf[slot];
+  return GDSP_OK;
+}
+
+namespace {
 
 // Host <-> device copies through library-owned pinned staging buffers (two
 // halves, double-buffered). The caller's memory is only touched by memcpy on
@@ -214,11 +207,9 @@ int gdsp_api::copy_h2d(void *dst, const void *src, size_t bytes, hipStream_t s) 
   return GDSP_OK;
 }
 
-namespace {
-
 // Device -> host, double-buffered; returns once every chunk has landed in
 // dst, so everything queued on s before it has completed too.
-int copy_d2h(void *dst, const void *src, size_t bytes, hipStream_t s) {
+int gdsp_api::copy_d2h(void *dst, const void *src, size_t bytes, hipStream_t s) {
   Staging *st = nullptr;
   STCHK(staging_get(&st));
   const size_t nchunk = (bytes + st->half - 1) / st->half;
@@ -242,6 +233,26 @@ int copy_d2h(void *dst, const void *src, size_t bytes, hipStream_t s) {
   }
   return GDSP_OK;
 }
+
+int gdsp_api::stage_rows(double *d, const double *h, int64_t rows, int64_t n, int64_t ld,
+                         int64_t lx, hipStream_t s) {
+  if (lx > n) HIPCHK(hipMemsetAsync(d, 0, (size_t)rows * (size_t)lx * sizeof(double), s));
+  if (lx == n && (ld == n || rows == 1))
+    return copy_h2d(d, h, (size_t)rows * (size_t)n * sizeof(double), s);
+  for (int64_t c = 0; c < rows; ++c)
+    STCHK(copy_h2d(d + c * lx, h + c * ld, (size_t)n * sizeof(double), s));
+  return GDSP_OK;
+}
+
+int gdsp_api::unstage_rows(double *h, const double *d, int64_t rows, int64_t n, int64_t ld,
+                           hipStream_t s) {
+  if (ld == n || rows == 1) return copy_d2h(h, d, (size_t)rows * (size_t)n * sizeof(double), s);
+  for (int64_t c = 0; c < rows; ++c)
+    STCHK(copy_d2h(h + c * ld, d + c * n, (size_t)n * sizeof(double), s));
+  return GDSP_OK;
+}
+
+namespace {
 
 // Mapped pinned host memory per (thread, device) for small host calls
 // (input at 0, output at kZeroCopyOut): the kernels access it over the
@@ -721,9 +732,11 @@ int exec_plan_depth(const gdsp_plan *p, const void *in, cd *out, int64_t batch, 
   return fail(GDSP_ERR_INVALID, "bad plan kind");
 }
 
+}  // namespace
+
 // Host-pointer batched transform: H2D, exec, D2H, synchronise.
-int host_batch(const void *x, size_t in_elem_bytes, double *out, int64_t n, int64_t batch,
-               bool inv, int load) {
+int gdsp_api::host_batch(const void *x, size_t in_elem_bytes, double *out, int64_t n,
+                         int64_t batch, bool inv, int load) {
   if (n < 0 || batch < 0) return fail(GDSP_ERR_INVALID, "negative size");
   if (batch == 0) return GDSP_OK;
   if (n == 0) {
@@ -757,42 +770,13 @@ int host_batch(const void *x, size_t in_elem_bytes, double *out, int64_t n, int6
   DevBuf din, dout;
   STCHK(din.alloc(in_bytes, s, SLOT_IN));
   STCHK(dout.alloc(out_bytes, s, SLOT_OUT));
-  STCHK(copy_h2d(din.p, x, in_bytes, s));
-  const int st = exec_plan(p, din.p, (cd *)dout.p, batch, inv, load, s);
-  if (st != GDSP_OK) {
-    (void)hipStreamSynchronize(s);  // queued copies still read the staging halves
-    return st;
-  }
+  STCHK(run_queued(s, [&]() -> int {
+    STCHK(copy_h2d(din.p, x, in_bytes, s));
+    return exec_plan(p, din.p, (cd *)dout.p, batch, inv, load, s);
+  }));
   STCHK(copy_d2h(out, dout.p, out_bytes, s));  // returns after the stream drained
   return GDSP_OK;
 }
-
-void hann_table(int64_t L, double *r) {  // window/window.go:62-76
-  if (L <= 0) return;
-  if (L == 1) {
-    r[0] = 1;
-    return;
-  }
-  const int64_t N = L - 1;
-  const double coef = 2 * M_PI / (double)N;
-  for (int64_t i = 0; i <= N; ++i) r[i] = 0.5 * (1 - cos(coef * (double)i));
-}
-
-int segment_count(int64_t lx, int64_t size, int64_t noverlap, int64_t *count) {
-  const int64_t stride = size - noverlap;  // spectral/spectral.go:22-33
-  if (lx == size) {
-    *count = 1;
-  } else if (lx > size) {
-    if (stride == 0) return fail(GDSP_ERR_DIVIDE_BY_ZERO, "integer divide by zero");
-    *count = (lx - size) / stride + 1;
-    if (*count < 0) return fail(GDSP_ERR_INVALID, "makeslice: len out of range");
-  } else {
-    *count = 0;
-  }
-  return GDSP_OK;
-}
-
-}  // namespace
 
 // Configuration (launch.hpp): the deployment knobs, the development build's
 // experiment switches and the algorithm flags.
@@ -812,33 +796,6 @@ unsigned algo_flags() {
   return gdsp_api::build_flags(&f) ? f : g_algo.load(std::memory_order_relaxed);
 }
 }  // namespace gdsp
-
-// Forwarders for the multi-device layer (api_internal.hpp, multi.hip).
-namespace gdsp_api {
-int set_error(int st, const std::string &msg) { return fail(st, msg); }
-hipStream_t stream_for(int dev) { return thread_stream(dev); }
-int scratch(size_t bytes, hipStream_t s, ScratchSlot slot, void **p) {
-  static const Slot map[] = {SLOT_IN, SLOT_AUX, SLOT_AUX2};
-  DevBuf b;
-  STCHK(b.alloc(bytes, s, map[slot]));
-  *p = b.p;
-  return GDSP_OK;
-}
-int h2d(void *dst, const void *src, size_t bytes, hipStream_t s) {
-  return copy_h2d(dst, src, bytes, s);
-}
-int d2h(void *dst, const void *src, size_t bytes, hipStream_t s) {
-  return copy_d2h(dst, src, bytes, s);
-}
-int batch_on_current_device(const void *x, size_t in_elem_bytes, double *out, int64_t n,
-                            int64_t batch, bool inv, int load) {
-  return host_batch(x, in_elem_bytes, out, n, batch, inv, load);
-}
-void hann(int64_t L, double *out) { hann_table(L, out); }
-int segments(int64_t lx, int64_t size, int64_t noverlap, int64_t *count) {
-  return segment_count(lx, size, noverlap, count);
-}
-}  // namespace gdsp_api
 
 // ============================================================================
 // C ABI
@@ -1007,14 +964,11 @@ int gdsp_convolve_batch(const double *x, const double *y, double *out, int64_t n
   STCHK(dx.alloc(xb, s, SLOT_IN));
   STCHK(dy.alloc(2 * yb, s, SLOT_AUX));  // y, then its spectrum
   cd *py = (cd *)dy.p;
-  STCHK(copy_h2d(dx.p, x, xb, s));
-  STCHK(copy_h2d(py, y, yb, s));
-  const int st = convolve_rows(p, (const cd *)dx.p, py, y_rows, (cd *)dx.p, batch,
-                               py + y_rows * n, s);
-  if (st != GDSP_OK) {
-    (void)hipStreamSynchronize(s);  // queued copies still read the staging halves
-    return st;
-  }
+  STCHK(run_queued(s, [&]() -> int {
+    STCHK(copy_h2d(dx.p, x, xb, s));
+    STCHK(copy_h2d(py, y, yb, s));
+    return convolve_rows(p, (const cd *)dx.p, py, y_rows, (cd *)dx.p, batch, py + y_rows * n, s);
+  }));
   STCHK(copy_d2h(out, dx.p, xb, s));  // returns after the stream drained
   return GDSP_OK;
 }
@@ -1208,33 +1162,21 @@ int gdsp_fir_batch(const double *x, int64_t ldx, const double *h, int64_t h_rows
   STCHK(current_device(&dev));
   hipStream_t s = thread_stream(dev);
   if (!s) return fail(GDSP_ERR_HIP, "stream creation failed");
-  const size_t xrow = (size_t)n * sizeof(double), orow = (size_t)out_len * sizeof(double);
   DevBuf dx, dh, dout, dw;
-  STCHK(dx.alloc((size_t)channels * xrow, s, SLOT_IN));
+  STCHK(dx.alloc((size_t)channels * (size_t)n * sizeof(double), s, SLOT_IN));
   STCHK(dh.alloc((size_t)h_rows * (size_t)m * sizeof(double), s, SLOT_FIR_H));
-  STCHK(dout.alloc((size_t)channels * orow, s, SLOT_FIR_OUT));
+  STCHK(dout.alloc((size_t)channels * (size_t)out_len * sizeof(double), s, SLOT_FIR_OUT));
   STCHK(dw.alloc(fir_work_bytes(F, m, h_rows, channels, out_len, fr), s, SLOT_FIR));
   double *px = (double *)dx.p, *po = (double *)dout.p;
-  auto queue = [&]() -> int {
-    if (channels == 1 || ldx == n) {
-      STCHK(copy_h2d(px, x, (size_t)channels * xrow, s));
-    } else {
-      for (int64_t c = 0; c < channels; ++c) STCHK(copy_h2d(px + c * n, x + c * ldx, xrow, s));
-    }
+  STCHK(run_queued(s, [&]() -> int {
+    STCHK(stage_rows(px, x, channels, n, ldx, n, s));
     STCHK(copy_h2d(dh.p, h, (size_t)h_rows * (size_t)m * sizeof(double), s));
     return fir_rows(px, n, (const double *)dh.p, h_rows, m, channels, n, out_len, F, fr, po,
                     out_len, (cd *)dw.p, s);
-  };
-  const int st = queue();
-  if (st != GDSP_OK) {
-    (void)hipStreamSynchronize(s);  // queued copies still read the staging halves
-    return st;
-  }
+  }));
   // every sample left the caller's memory before the first result lands in
   // it, so out may alias x
-  if (channels == 1 || ldo == out_len) return copy_d2h(out, po, (size_t)channels * orow, s);
-  for (int64_t c = 0; c < channels; ++c) STCHK(copy_d2h(out + c * ldo, po + c * out_len, orow, s));
-  return GDSP_OK;
+  return unstage_rows(out, po, channels, out_len, ldo, s);
 }
 
 int gdsp_fft2_device(const void *d_in, void *d_out, int64_t rows, int64_t cols, int inverse,
@@ -1454,17 +1396,6 @@ int gdsp_ensure_plan(int64_t n) {
 void gdsp_set_worker_pool_size(int n) { g_worker_pool_size = n < 0 ? 0 : n; }
 int gdsp_worker_pool_size(void) { return g_worker_pool_size; }
 
-int gdsp_segment_count(int64_t lx, int64_t size, int64_t noverlap, int64_t *count) {
-  if (!count) return fail(GDSP_ERR_INVALID, "NULL pointer");
-  return segment_count(lx, size, noverlap, count);
-}
-
-int gdsp_window_hann(int64_t L, double *out) {
-  if (L < 0) return fail(GDSP_ERR_INVALID, "negative size");
-  hann_table(L, out);
-  return GDSP_OK;
-}
-
 int gdsp_plan_create(int64_t n, gdsp_plan **plan) {
   if (n < 0 || !plan) return fail(GDSP_ERR_INVALID, "bad argument");
   return get_plan(n, plan);
@@ -1527,631 +1458,6 @@ int gdsp_fft_real_batch_device(const gdsp_plan *plan, const double *d_in, void *
     return exec_plan(plan, d_out, (cd *)d_out, batch, true, gdsp::LOAD_COMPLEX, s);
   }
   return exec_plan(plan, d_in, (cd *)d_out, batch, inverse != 0, gdsp::LOAD_REAL, s);
-}
-
-int gdsp_pwelch_accumulate_device(const double *d_x, int64_t n, int64_t nfft, int64_t pad,
-                                  int64_t noverlap, int64_t seg_begin, int64_t seg_end,
-                                  const double *d_win_seg, double *d_acc, void *stream) {
-  if (nfft <= 0 || pad <= 0 || seg_begin < 0 || seg_end < seg_begin)
-    return fail(GDSP_ERR_INVALID, "bad Pwelch geometry");
-  if (seg_end == seg_begin) return GDSP_OK;
-  const int64_t stride = nfft - noverlap;
-  if ((seg_end - 1) * stride + nfft > n && seg_end > 1)
-    return fail(GDSP_ERR_INVALID, "segments exceed the signal");
-  const int64_t flen = pad > nfft ? pad : nfft;
-  hipStream_t s = (hipStream_t)stream;  // NULL = the null stream
-  gdsp_plan *p = nullptr;
-  STCHK(get_plan(flen, &p));
-  const int64_t nseg = seg_end - seg_begin;
-  // The fused kernels address a pair's (or a wave's group of pairs') samples
-  // with 32-bit offsets from one base; a very negative Noverlap (spectral.go:
-  // 22-43 allows it) spreads the segments beyond that, so strides above 2^22
-  // samples take the materialised path, which indexes in 64 bits.
-  const bool fused = stride <= ((int64_t)1 << 22);
-  if (fused && p->kind == KIND_LDS && gdsp::pwelch_wave_applies(p->log2n)) {
-    // 64 <= F <= 1024: wave-resident transforms, no workgroup barriers
-    // (pwelch_wave.hip), every wave a persistent worker over pair groups;
-    // F = 2048: two-wave workgroups
-    const bool half = 2 * noverlap == nfft && flen == nfft;
-    int64_t gpw = 0, nblk = 0, nrows = 0;
-    gdsp::pwelch_wave_geometry(p->log2n, half, nseg, &gpw, &nblk, &nrows);
-    DevBuf part, red;
-    STCHK(part.alloc((size_t)nrows * (size_t)flen * sizeof(double), s, SLOT_PW_PART));
-    STCHK(red.alloc((size_t)gdsp::reduce_scratch_doubles(nrows, flen) * sizeof(double), s,
-                    SLOT_PW_RED));
-    HIPCHK(gdsp::launch_pwelch_wave(p->log2n, half, d_x, nfft, stride, seg_begin, seg_end, gpw,
-                                    nblk, d_win_seg, p->tw, (double *)part.p, s));
-    HIPCHK(gdsp::launch_reduce_partials((const double *)part.p, nrows, flen, d_acc,
-                                        (double *)red.p, s));
-    return GDSP_OK;
-  }
-  if (fused && p->kind == KIND_LDS && p->log2n >= 4) {
-    // fused path: packed segment pairs, persistent workers over contiguous
-    // pair ranges (the 50 % overlap of consecutive pairs is re-read from L2)
-    const int64_t npairs = (nseg + 1) / 2;
-    // workers per workgroup slot: 512 / 1024 / 4096 measured 2.86 / 2.81 /
-    // 2.77 against 2.76 ms for 2048 (BASELINE configs[4])
-    constexpr int64_t wmul = 2048;
-    int64_t target = wmul * (int64_t)gdsp::pwelch_workers_per_block(p->log2n);
-    if (target > npairs) target = npairs;
-    const int64_t ppw = (npairs + target - 1) / target;
-    const int64_t nworkers = (npairs + ppw - 1) / ppw;
-    DevBuf part, red;
-    STCHK(part.alloc((size_t)nworkers * (size_t)flen * sizeof(double), s, SLOT_PW_PART));
-    STCHK(red.alloc((size_t)gdsp::reduce_scratch_doubles(nworkers, flen) * sizeof(double), s,
-                    SLOT_PW_RED));
-    if (2 * noverlap == nfft && flen == nfft && p->log2n >= 5) {
-      // half overlap: each sample loaded once, window in LDS
-      HIPCHK(gdsp::launch_pwelch_half(p->log2n, d_x, seg_begin, seg_end, ppw, nworkers, d_win_seg,
-                                      p->tw, (double *)part.p, s));
-    } else if (p->log2n == 12 && flen == nfft) {
-      // any other overlap at 4096: the row kernel's structure without the carry
-      HIPCHK(gdsp::launch_pwelch_rowg4096(d_x, stride, seg_begin, seg_end, ppw, nworkers,
-                                          d_win_seg, p->tw, (double *)part.p, s));
-    } else {
-      HIPCHK(gdsp::launch_pwelch(p->log2n, d_x, nfft, stride, seg_begin, seg_end, ppw, nworkers,
-                                 d_win_seg, p->tw, (double *)part.p, s));
-    }
-    HIPCHK(gdsp::launch_reduce_partials((const double *)part.p, nworkers, flen, d_acc,
-                                        (double *)red.p, s));
-    return GDSP_OK;
-  }
-  // the fused Pwelch on a compiled or runtime-compiled specialisation, on the
-  // Pwelch's own list where it has one (md_pw); 0 workers per block where its
-  // kernel cannot stage a pair this far apart (negative Noverlap)
-  const bool own = p->md_pw.n > 0 && !p->jit;
-  const gdsp::MixedDesc &pmd = own ? p->md_pw : p->md;
-  const int wpb_fixed =
-      !fused || p->kind != KIND_MIXED ? 0
-      : p->jit                        ? gdsp::jit_pw_tpw(p->jit, stride + nfft)
-                                      : gdsp::pwelch_fixed_workers_per_block(pmd, stride + nfft);
-  if (wpb_fixed > 0 && !(gdsp::algo_flags() & GDSP_ALGO_GENERIC_MIXED)) {
-    // fused path on a compiled specialisation (e.g. NFFT 1000, 3000)
-    const cd *ptw = own ? p->tw_pw : p->tw;
-    const int64_t npairs = (nseg + 1) / 2;
-    const int wpb = wpb_fixed;
-    int64_t target = 2048 * (int64_t)wpb;
-    if (target > npairs) target = npairs;
-    const int64_t ppw = (npairs + target - 1) / target;
-    const int64_t nworkers = (npairs + ppw - 1) / ppw;
-    DevBuf part, red;
-    STCHK(part.alloc((size_t)nworkers * (size_t)flen * sizeof(double), s, SLOT_PW_PART));
-    STCHK(red.alloc((size_t)gdsp::reduce_scratch_doubles(nworkers, flen) * sizeof(double), s,
-                    SLOT_PW_RED));
-    if (p->jit)
-      HIPCHK(gdsp::jit_launch_pwelch(p->jit, d_x, nfft, stride, seg_begin, seg_end, ppw, nworkers,
-                                     d_win_seg, p->tw, (double *)part.p, s));
-    else
-      HIPCHK(gdsp::launch_pwelch_fixed(pmd, d_x, nfft, stride, seg_begin, seg_end, ppw,
-                                       nworkers, d_win_seg, ptw, (double *)part.p, s));
-    HIPCHK(gdsp::launch_reduce_partials((const double *)part.p, nworkers, flen, d_acc,
-                                        (double *)red.p, s));
-    return GDSP_OK;
-  }
-  if (fused && p->kind == KIND_MIXED && p->md_gen.npass >= 2) {
-    // fused mixed-radix path (smooth NFFT / Pad up to 4096)
-    const int64_t npairs = (nseg + 1) / 2;
-    int64_t target = 2048;
-    if (target > npairs) target = npairs;
-    const int64_t ppw = (npairs + target - 1) / target;
-    const int64_t nworkers = (npairs + ppw - 1) / ppw;
-    DevBuf part, red;
-    STCHK(part.alloc((size_t)nworkers * (size_t)flen * sizeof(double), s, SLOT_PW_PART));
-    STCHK(red.alloc((size_t)gdsp::reduce_scratch_doubles(nworkers, flen) * sizeof(double), s,
-                    SLOT_PW_RED));
-    HIPCHK(gdsp::launch_pwelch_mixed(p->md_gen, d_x, nfft, stride, seg_begin, seg_end, ppw,
-                                     nworkers, d_win_seg, p->tw_gen, (double *)part.p, s));
-    HIPCHK(gdsp::launch_reduce_partials((const double *)part.p, nworkers, flen, d_acc,
-                                        (double *)red.p, s));
-    return GDSP_OK;
-  }
-  // materialised path (lengths without a fused kernel): packed segment pairs
-  // as complex rows, the batched FFT of the plan, per-bin partial power sums,
-  // deterministic reduction into acc
-  const int64_t nrows_all = (nseg + 1) / 2;
-  int64_t rows = ((int64_t)1 << 25) / flen;  // 512 MiB of rows per chunk
-  constexpr int64_t kRpp = 64;
-  if (rows < 1) rows = 1;
-  if (rows > 65535 * kRpp) rows = 65535 * kRpp;  // partial-sum grid limit
-  if (rows > nrows_all) rows = nrows_all;
-  const int64_t parts = (rows + kRpp - 1) / kRpp;
-  DevBuf buf, part, red;
-  STCHK(buf.alloc((size_t)rows * (size_t)flen * sizeof(cd), s, SLOT_PW_BUF));
-  STCHK(part.alloc((size_t)parts * (size_t)flen * sizeof(double), s, SLOT_PW_PART));
-  STCHK(red.alloc((size_t)gdsp::reduce_scratch_doubles(parts, flen) * sizeof(double), s,
-                  SLOT_PW_RED));
-  for (int64_t r0 = 0; r0 < nrows_all; r0 += rows) {
-    const int64_t nr = (nrows_all - r0) < rows ? (nrows_all - r0) : rows;
-    HIPCHK(gdsp::launch_segments_to_complex(d_x, nfft, flen, stride, seg_begin + 2 * r0, seg_end,
-                                            nr, d_win_seg, (cd *)buf.p, s));
-    STCHK(exec_plan(p, buf.p, (cd *)buf.p, nr, false, gdsp::LOAD_COMPLEX, s));
-    HIPCHK(gdsp::launch_power_partials((const cd *)buf.p, nr, flen, kRpp, (double *)part.p, s));
-    HIPCHK(gdsp::launch_reduce_partials((const double *)part.p, (nr + kRpp - 1) / kRpp, flen,
-                                        d_acc, (double *)red.p, s));
-  }
-  return GDSP_OK;
-}
-
-int gdsp_pwelch_finalize(const double *acc, int64_t flen, int64_t nsegs, int64_t nfft,
-                         int64_t pad, const double *win_nfft, double fs, int scale_off,
-                         double *pxx, double *freqs) {
-  // spectral/pwelch.go:113-142
-  if (flen <= 0 || nfft <= 0 || pad <= 0 || !pxx || !freqs)
-    return fail(GDSP_ERR_INVALID, "bad argument");
-  const int64_t lp = pad / 2 + 1;
-  std::vector<double> hw;
-  if (!win_nfft) {
-    hw.resize((size_t)nfft);
-    hann_table(nfft, hw.data());
-    win_nfft = hw.data();
-  }
-  double norm = 0;
-  for (int64_t i = 0; i < nfft; ++i) norm += win_nfft[i] * win_nfft[i];
-  if (!scale_off) norm *= fs;
-  for (int64_t j = 0; j < lp; ++j) {
-    double d = 0.0;
-    if (nsegs > 0) {
-      d = 0.5 * (acc[j] + acc[(flen - j) % flen]) / (double)nsegs;
-      if (j > 0 && j < lp - 1) d *= 2;
-    }
-    pxx[j] = d / norm;
-  }
-  const double coef = fs / (double)pad;
-  for (int64_t j = 0; j < lp; ++j) freqs[j] = (double)j * coef;
-  return GDSP_OK;
-}
-
-int gdsp_pwelch(const double *x, int64_t n, double fs, int64_t nfft, int64_t pad,
-                int64_t noverlap, const double *win_seg, const double *win_nfft, int scale_off,
-                double *pxx, double *freqs, int64_t *lp_out) {
-  // spectral/pwelch.go:74-145
-  if (!lp_out) return fail(GDSP_ERR_INVALID, "NULL pointer");
-  *lp_out = 0;
-  if (n < 0) return fail(GDSP_ERR_INVALID, "negative size");
-  if (n == 0) return GDSP_OK;
-  if (nfft == 0) nfft = 256;
-  if (pad == 0) pad = nfft;
-  if (nfft < 0 || pad < 0) return fail(GDSP_ERR_INVALID, "negative NFFT/Pad");
-  const int64_t lx = n < nfft ? nfft : n;  // dsputils.ZeroPadF(x, nfft)
-  int64_t nsegs = 0;
-  STCHK(segment_count(lx, nfft, noverlap, &nsegs));
-  const int64_t flen = pad > nfft ? pad : nfft;
-  const int64_t lp = pad / 2 + 1;
-  std::vector<double> hseg, hnfft;
-  if (!win_seg) {
-    hseg.resize((size_t)flen);
-    hann_table(flen, hseg.data());
-    win_seg = hseg.data();
-  }
-  if (!win_nfft) {
-    hnfft.resize((size_t)nfft);
-    hann_table(nfft, hnfft.data());
-    win_nfft = hnfft.data();
-  }
-  if (nsegs >= 2 && gdsp_api::multi_wanted((size_t)n * sizeof(double), nsegs))
-    return gdsp_api::pwelch_multi(x, n, fs, nfft, pad, noverlap, win_seg, win_nfft, scale_off, pxx,
-                                  freqs, lp_out, nullptr, 0);
-  std::vector<double> acc((size_t)flen, 0.0);
-  if (nsegs > 0) {
-    int dev = 0;
-    STCHK(current_device(&dev));
-    hipStream_t s = thread_stream(dev);
-    DevBuf dx, dw, dacc;
-    STCHK(dx.alloc((size_t)lx * sizeof(double), s, SLOT_IN));
-    STCHK(dw.alloc((size_t)flen * sizeof(double), s, SLOT_AUX));
-    STCHK(dacc.alloc((size_t)flen * sizeof(double), s, SLOT_AUX2));
-    if (lx > n) HIPCHK(hipMemsetAsync(dx.p, 0, (size_t)lx * sizeof(double), s));
-    STCHK(copy_h2d(dx.p, x, (size_t)n * sizeof(double), s));
-    STCHK(copy_h2d(dw.p, win_seg, (size_t)flen * sizeof(double), s));
-    HIPCHK(hipMemsetAsync(dacc.p, 0, (size_t)flen * sizeof(double), s));
-    STCHK(gdsp_pwelch_accumulate_device((const double *)dx.p, lx, nfft, pad, noverlap, 0, nsegs,
-                                        (const double *)dw.p, (double *)dacc.p, s));
-    STCHK(copy_d2h(acc.data(), dacc.p, (size_t)flen * sizeof(double), s));
-  }
-  STCHK(gdsp_pwelch_finalize(acc.data(), flen, nsegs, nfft, pad, win_nfft, fs, scale_off, pxx,
-                             freqs));
-  *lp_out = lp;
-  return GDSP_OK;
-}
-
-// ---- batched Pwelch: the channels of a planar batch in one call ---------------
-// The batched kernel (pwelch_batch.hip) serves the lengths of the wave
-// kernels; every other length and stride, and any shape under
-// GDSP_ALGO_NO_FUSED_PWELCH_BATCH, loops over the channels with
-// gdsp_pwelch_accumulate_device. Host arithmetic only.
-static bool pwelch_batch_fused(int64_t flen, int64_t stride) {
-  return flen > 0 && gdsp_api::is_pow2(flen) &&
-         gdsp::pwelch_batch_applies(gdsp_api::ilog2(flen)) && stride <= ((int64_t)1 << 22) &&
-         !(g_algo.load() & GDSP_ALGO_NO_FUSED_PWELCH_BATCH);
-}
-
-int gdsp_pwelch_batch_fused(int64_t channels, int64_t n, int64_t nfft, int64_t pad,
-                            int64_t noverlap) {
-  if (channels < 0 || n < 0) return 0;
-  if (nfft == 0) nfft = 256;
-  if (pad == 0) pad = nfft;
-  if (nfft < 0 || pad < 0) return 0;
-  return pwelch_batch_fused(pad > nfft ? pad : nfft, nfft - noverlap) ? 1 : 0;
-}
-
-int gdsp_pwelch_batch_accumulate_device(const double *d_x, int64_t channels, int64_t n,
-                                        int64_t ldx, int64_t nfft, int64_t pad, int64_t noverlap,
-                                        int64_t seg_begin, int64_t seg_end,
-                                        const double *d_win_seg, double *d_acc, void *stream) {
-  if (nfft <= 0 || pad <= 0 || seg_begin < 0 || seg_end < seg_begin)
-    return fail(GDSP_ERR_INVALID, "bad Pwelch geometry");
-  if (channels < 0 || n < 0 || (channels > 1 && ldx < n))
-    return fail(GDSP_ERR_INVALID, "bad batch geometry");
-  if (channels == 0 || seg_end == seg_begin) return GDSP_OK;
-  if (!d_x || !d_win_seg || !d_acc) return fail(GDSP_ERR_INVALID, "NULL pointer");
-  const int64_t stride = nfft - noverlap;
-  if ((seg_end - 1) * stride + nfft > n && seg_end > 1)
-    return fail(GDSP_ERR_INVALID, "segments exceed the signal");
-  const int64_t flen = pad > nfft ? pad : nfft;
-  hipStream_t s = (hipStream_t)stream;
-  gdsp_plan *p = nullptr;
-  if (pwelch_batch_fused(flen, stride)) STCHK(get_plan(flen, &p));
-  if (!p || p->kind != KIND_LDS) {
-    for (int64_t c = 0; c < channels; ++c)
-      STCHK(gdsp_pwelch_accumulate_device(d_x + c * ldx, n, nfft, pad, noverlap, seg_begin,
-                                          seg_end, d_win_seg, d_acc + c * flen, stream));
-    return GDSP_OK;
-  }
-  const bool half = 2 * noverlap == nfft && flen == nfft;
-  int64_t wpc = 0, gpw = 0, rows = 0;
-  gdsp::pwelch_batch_geometry(p->log2n, half, channels, seg_end - seg_begin, &wpc, &gpw, &rows);
-  // channels per launch: the partials within the materialised path's 512 MiB
-  int64_t cpl = ((int64_t)1 << 26) / (rows * flen);
-  if (cpl < 1) cpl = 1;
-  if (cpl > channels) cpl = channels;
-  DevBuf part, red;
-  STCHK(part.alloc((size_t)cpl * (size_t)rows * (size_t)flen * sizeof(double), s, SLOT_PW_PART));
-  STCHK(red.alloc((size_t)gdsp::reduce_batch_scratch_doubles(cpl, rows, flen) * sizeof(double), s,
-                  SLOT_PW_RED));
-  for (int64_t c0 = 0; c0 < channels; c0 += cpl) {
-    const int64_t nc = channels - c0 < cpl ? channels - c0 : cpl;
-    HIPCHK(gdsp::launch_pwelch_batch(p->log2n, half, d_x + c0 * ldx, ldx, nc, wpc, nfft, stride,
-                                     seg_begin, seg_end, gpw, d_win_seg, p->tw, (double *)part.p,
-                                     s));
-    HIPCHK(gdsp::launch_reduce_batch((const double *)part.p, nc, rows, flen, d_acc + c0 * flen,
-                                     (double *)red.p, s));
-  }
-  return GDSP_OK;
-}
-
-int gdsp_pwelch_batch_finalize_device(const double *d_acc, int64_t channels, int64_t flen,
-                                      int64_t nsegs, int64_t nfft, int64_t pad,
-                                      const double *win_nfft, double fs, int scale_off,
-                                      double *d_pxx, double *freqs, void *stream) {
-  if (channels < 0 || flen <= 0 || nfft <= 0 || pad <= 0 || nsegs < 0)
-    return fail(GDSP_ERR_INVALID, "bad argument");
-  if (channels > 0 && (!d_acc || !d_pxx)) return fail(GDSP_ERR_INVALID, "NULL pointer");
-  const int64_t lp = pad / 2 + 1;
-  if (lp > flen) return fail(GDSP_ERR_INVALID, "accumulators shorter than Pad / 2 + 1");
-  std::vector<double> hw;
-  if (!win_nfft) {
-    hw.resize((size_t)nfft);
-    hann_table(nfft, hw.data());
-    win_nfft = hw.data();
-  }
-  double norm = 0;  // as gdsp_pwelch_finalize
-  for (int64_t i = 0; i < nfft; ++i) norm += win_nfft[i] * win_nfft[i];
-  if (!scale_off) norm *= fs;
-  if (freqs) {
-    const double coef = fs / (double)pad;
-    for (int64_t j = 0; j < lp; ++j) freqs[j] = (double)j * coef;
-  }
-  if (channels == 0) return GDSP_OK;
-  HIPCHK(gdsp::launch_pwelch_finalize(d_acc, channels, flen, lp, nsegs, norm, d_pxx,
-                                      (hipStream_t)stream));
-  return GDSP_OK;
-}
-
-int gdsp_pwelch_batch(const double *x, int64_t channels, int64_t n, int64_t ldx, double fs,
-                      int64_t nfft, int64_t pad, int64_t noverlap, const double *win_seg,
-                      const double *win_nfft, int scale_off, double *pxx, double *freqs,
-                      int64_t *lp_out) {
-  if (!lp_out) return fail(GDSP_ERR_INVALID, "NULL pointer");
-  *lp_out = 0;
-  if (channels < 0 || n < 0) return fail(GDSP_ERR_INVALID, "negative size");
-  if (n == 0) return GDSP_OK;
-  if (nfft == 0) nfft = 256;
-  if (pad == 0) pad = nfft;
-  if (nfft < 0 || pad < 0) return fail(GDSP_ERR_INVALID, "negative NFFT/Pad");
-  if (channels > 1 && ldx < n) return fail(GDSP_ERR_INVALID, "ldx below the channel length");
-  const int64_t lx = n < nfft ? nfft : n;  // dsputils.ZeroPadF(x, nfft) per channel
-  int64_t nsegs = 0;
-  STCHK(segment_count(lx, nfft, noverlap, &nsegs));
-  if (!freqs || (channels > 0 && (!x || !pxx))) return fail(GDSP_ERR_INVALID, "NULL pointer");
-  const int64_t flen = pad > nfft ? pad : nfft;
-  const int64_t lp = pad / 2 + 1;
-  std::vector<double> hseg, hnfft;
-  if (!win_seg) {
-    hseg.resize((size_t)flen);
-    hann_table(flen, hseg.data());
-    win_seg = hseg.data();
-  }
-  if (!win_nfft) {
-    hnfft.resize((size_t)nfft);
-    hann_table(nfft, hnfft.data());
-    win_nfft = hnfft.data();
-  }
-  if (channels == 0) {
-    const double coef = fs / (double)pad;
-    for (int64_t j = 0; j < lp; ++j) freqs[j] = (double)j * coef;
-    *lp_out = lp;
-    return GDSP_OK;
-  }
-  std::vector<double> acc((size_t)channels * (size_t)flen, 0.0);
-  if (nsegs > 0) {
-    int dev = 0;
-    STCHK(current_device(&dev));
-    hipStream_t s = thread_stream(dev);
-    if (!s) return fail(GDSP_ERR_HIP, "stream creation failed");
-    const size_t abytes = acc.size() * sizeof(double);
-    DevBuf dx, dw, dacc;
-    STCHK(dx.alloc((size_t)channels * (size_t)lx * sizeof(double), s, SLOT_IN));
-    STCHK(dw.alloc((size_t)flen * sizeof(double), s, SLOT_AUX));
-    STCHK(dacc.alloc(abytes, s, SLOT_AUX2));
-    double *px = (double *)dx.p;
-    int st = GDSP_OK;
-    if (lx > n && hipMemsetAsync(px, 0, (size_t)channels * (size_t)lx * sizeof(double), s) !=
-                      hipSuccess)
-      st = fail(GDSP_ERR_HIP, "hipMemsetAsync failed");
-    if (st == GDSP_OK && lx == n && (ldx == n || channels == 1)) {
-      st = copy_h2d(px, x, (size_t)channels * (size_t)n * sizeof(double), s);
-    } else {
-      for (int64_t c = 0; c < channels && st == GDSP_OK; ++c)
-        st = copy_h2d(px + c * lx, x + c * ldx, (size_t)n * sizeof(double), s);
-    }
-    if (st == GDSP_OK) st = copy_h2d(dw.p, win_seg, (size_t)flen * sizeof(double), s);
-    if (st == GDSP_OK && hipMemsetAsync(dacc.p, 0, abytes, s) != hipSuccess)
-      st = fail(GDSP_ERR_HIP, "hipMemsetAsync failed");
-    if (st == GDSP_OK)
-      st = gdsp_pwelch_batch_accumulate_device(px, channels, lx, lx, nfft, pad, noverlap, 0, nsegs,
-                                               (const double *)dw.p, (double *)dacc.p, s);
-    if (st != GDSP_OK) {
-      (void)hipStreamSynchronize(s);  // queued copies still read the staging halves
-      return st;
-    }
-    STCHK(copy_d2h(acc.data(), dacc.p, abytes, s));
-  }
-  for (int64_t c = 0; c < channels; ++c)
-    STCHK(gdsp_pwelch_finalize(acc.data() + c * flen, flen, nsegs, nfft, pad, win_nfft, fs,
-                               scale_off, pxx + c * lp, freqs));
-  *lp_out = lp;
-  return GDSP_OK;
-}
-
-// ---- batched cross spectra: Cpsd and coherence of x channels against y --------
-// The fused kernel (cpsd_batch.hip) serves the lengths of the batched Pwelch;
-// every other length and stride, and any shape under GDSP_ALGO_NO_FUSED_CPSD,
-// runs the materialised form. Host arithmetic only.
-static bool cpsd_batch_fused(int64_t flen, int64_t stride) {
-  return flen > 0 && gdsp_api::is_pow2(flen) && gdsp::cpsd_batch_applies(gdsp_api::ilog2(flen)) &&
-         stride <= ((int64_t)1 << 22) && !(g_algo.load() & GDSP_ALGO_NO_FUSED_CPSD);
-}
-
-int gdsp_cpsd_batch_fused(int64_t channels, int64_t n, int64_t nfft, int64_t pad,
-                          int64_t noverlap) {
-  if (channels < 0 || n < 0) return 0;
-  if (nfft == 0) nfft = 256;
-  if (pad == 0) pad = nfft;
-  if (nfft < 0 || pad < 0) return 0;
-  return cpsd_batch_fused(pad > nfft ? pad : nfft, nfft - noverlap) ? 1 : 0;
-}
-
-int gdsp_cpsd_batch_accumulate_device(const double *d_x, int64_t ldx, const double *d_y,
-                                      int64_t ldy, int64_t y_rows, int64_t channels, int64_t n,
-                                      int64_t nfft, int64_t pad, int64_t noverlap,
-                                      int64_t seg_begin, int64_t seg_end,
-                                      const double *d_win_seg, double *d_acc, void *stream) {
-  if (nfft <= 0 || pad <= 0 || seg_begin < 0 || seg_end < seg_begin)
-    return fail(GDSP_ERR_INVALID, "bad Cpsd geometry");
-  if (channels < 0 || n < 0 || y_rows < 0 || (channels > 1 && ldx < n) || (y_rows > 1 && ldy < n))
-    return fail(GDSP_ERR_INVALID, "bad batch geometry");
-  if (y_rows != 1 && y_rows != channels)
-    return fail(GDSP_ERR_UNEQUAL, "y is neither one row nor a row per channel");
-  const int64_t stride = nfft - noverlap;
-  // Segment divides by the stride only where there is more than one segment
-  if (stride == 0 && seg_end > 1) return fail(GDSP_ERR_DIVIDE_BY_ZERO, "integer divide by zero");
-  if (channels == 0 || seg_end == seg_begin) return GDSP_OK;
-  if (!d_x || !d_y || !d_win_seg || !d_acc) return fail(GDSP_ERR_INVALID, "NULL pointer");
-  // a negative stride (Noverlap > NFFT) leaves at most segment 0 (Segment)
-  if ((seg_end - 1) * stride + nfft > n || (stride < 0 && seg_end > 1))
-    return fail(GDSP_ERR_INVALID, "segments exceed the signal");
-  const int64_t flen = pad > nfft ? pad : nfft;
-  const int64_t hb = flen / 2 + 1, nseg = seg_end - seg_begin;
-  const int64_t ldyk = y_rows == 1 ? 0 : ldy;  // the kernels' y row stride
-  hipStream_t s = (hipStream_t)stream;
-  gdsp_plan *p = nullptr;
-  STCHK(get_plan(flen, &p));
-  DevBuf buf, part, red, bal;
-  // get_plan builds a power of 2 up to 2^14 as KIND_LDS under every flag set
-  // (build_plan, plan.hip), so gdsp_cpsd_batch_fused's answer holds here; the
-  // kind is checked because the kernel reads that plan's twiddle table
-  if (cpsd_batch_fused(flen, stride) && p->kind == KIND_LDS) {
-    int64_t wpc = 0, gpw = 0, rows = 0;
-    gdsp::cpsd_batch_geometry(p->log2n, channels, nseg, &wpc, &gpw, &rows);
-    // channels per launch: the partials within 512 MiB
-    int64_t cpl = ((int64_t)1 << 26) / (rows * 4 * hb);
-    if (cpl < 1) cpl = 1;
-    if (cpl > channels) cpl = channels;
-    STCHK(part.alloc((size_t)cpl * (size_t)rows * (size_t)(4 * hb) * sizeof(double), s,
-                     SLOT_PW_PART));
-    STCHK(red.alloc((size_t)gdsp::reduce_batch_scratch_doubles(cpl, rows, 4 * hb) * sizeof(double),
-                    s, SLOT_PW_RED));
-    for (int64_t c0 = 0; c0 < channels; c0 += cpl) {
-      const int64_t nc = channels - c0 < cpl ? channels - c0 : cpl;
-      HIPCHK(gdsp::launch_cpsd_batch(p->log2n, d_x + c0 * ldx, ldx, d_y + c0 * ldyk, ldyk, nc, wpc,
-                                     nfft, stride, seg_begin, seg_end, gpw, d_win_seg, p->tw,
-                                     (double *)part.p, s));
-      HIPCHK(gdsp::launch_reduce_batch((const double *)part.p, nc, rows, 4 * hb,
-                                       d_acc + c0 * 4 * hb, (double *)red.p, s));
-    }
-    return GDSP_OK;
-  }
-  // materialised form: chunks of at most 512 MiB of complex rows, whole
-  // channels where a channel's segments fit, else one channel's segments in
-  // runs; parts of kRpp rows, reduced in the fixed order
-  constexpr int64_t kRpp = 64;
-  int64_t maxrows = ((int64_t)1 << 25) / flen;
-  if (maxrows < 1) maxrows = 1;
-  const int64_t ns_max = nseg < maxrows ? nseg : maxrows;  // segments per run
-  int64_t cpl = maxrows / ns_max;                           // channels per launch
-  if (cpl > channels) cpl = channels;
-  const int64_t parts_max = (ns_max + kRpp - 1) / kRpp;
-  STCHK(buf.alloc((size_t)cpl * (size_t)ns_max * (size_t)flen * sizeof(cd), s, SLOT_PW_BUF));
-  STCHK(bal.alloc((size_t)cpl * (size_t)ns_max * sizeof(double), s, SLOT_CP_BAL));
-  double *alpha = (double *)bal.p;  // a power of 2 per row (cpsd_batch.hip, Balance)
-  STCHK(part.alloc((size_t)cpl * (size_t)parts_max * (size_t)(4 * hb) * sizeof(double), s,
-                   SLOT_PW_PART));
-  STCHK(red.alloc((size_t)gdsp::reduce_batch_scratch_doubles(cpl, parts_max, 4 * hb) *
-                      sizeof(double),
-                  s, SLOT_PW_RED));
-  for (int64_t c0 = 0; c0 < channels; c0 += cpl) {
-    const int64_t nc = channels - c0 < cpl ? channels - c0 : cpl;
-    for (int64_t j0 = 0; j0 < nseg; j0 += ns_max) {
-      const int64_t ns = nseg - j0 < ns_max ? nseg - j0 : ns_max;
-      HIPCHK(gdsp::launch_cpsd_balance(d_x + c0 * ldx, ldx, d_y + c0 * ldyk, ldyk, nc, ns, nfft,
-                                       stride, seg_begin + j0, d_win_seg, alpha, s));
-      HIPCHK(gdsp::launch_cpsd_gather(d_x + c0 * ldx, ldx, d_y + c0 * ldyk, ldyk, nc, ns, nfft,
-                                      flen, stride, seg_begin + j0, d_win_seg, alpha,
-                                      (cd *)buf.p, s));
-      STCHK(exec_plan(p, buf.p, (cd *)buf.p, nc * ns, false, gdsp::LOAD_COMPLEX, s));
-      HIPCHK(gdsp::launch_cpsd_partials((const cd *)buf.p, nc, ns, flen, kRpp, alpha,
-                                        (double *)part.p, s));
-      HIPCHK(gdsp::launch_reduce_batch((const double *)part.p, nc, (ns + kRpp - 1) / kRpp, 4 * hb,
-                                       d_acc + c0 * 4 * hb, (double *)red.p, s));
-    }
-  }
-  return GDSP_OK;
-}
-
-// the window's norm (spectral/pwelch.go:124-132) and the frequencies (:138-142)
-static double cpsd_norm_freqs(const double *win_nfft, int64_t nfft, int64_t pad, double fs,
-                              int scale_off, double *freqs) {
-  std::vector<double> hw;
-  if (!win_nfft) {
-    hw.resize((size_t)nfft);
-    hann_table(nfft, hw.data());
-    win_nfft = hw.data();
-  }
-  double norm = 0;  // as gdsp_pwelch_finalize
-  for (int64_t i = 0; i < nfft; ++i) norm += win_nfft[i] * win_nfft[i];
-  if (!scale_off) norm *= fs;
-  if (freqs) {
-    const double coef = fs / (double)pad;
-    for (int64_t j = 0; j < pad / 2 + 1; ++j) freqs[j] = (double)j * coef;
-  }
-  return norm;
-}
-
-int gdsp_cpsd_batch_finalize_device(const double *d_acc, int64_t channels, int64_t flen,
-                                    int64_t nsegs, int64_t nfft, int64_t pad,
-                                    const double *win_nfft, double fs, int scale_off,
-                                    void *d_pxy, double *d_pxx, double *d_pyy, double *d_coh,
-                                    double *freqs, void *stream) {
-  if (channels < 0 || flen <= 0 || nfft <= 0 || pad <= 0 || nsegs < 0)
-    return fail(GDSP_ERR_INVALID, "bad argument");
-  if (channels > 0 && !d_acc) return fail(GDSP_ERR_INVALID, "NULL pointer");
-  const int64_t lp = pad / 2 + 1, hb = flen / 2 + 1;
-  if (lp > hb) return fail(GDSP_ERR_INVALID, "accumulators shorter than Pad / 2 + 1");
-  const double norm = cpsd_norm_freqs(win_nfft, nfft, pad, fs, scale_off, freqs);
-  if (channels == 0 || (!d_pxy && !d_pxx && !d_pyy && !d_coh)) return GDSP_OK;
-  HIPCHK(gdsp::launch_cpsd_finalize(d_acc, channels, hb, lp, nsegs, norm, (cd *)d_pxy, d_pxx,
-                                    d_pyy, d_coh, (hipStream_t)stream));
-  return GDSP_OK;
-}
-
-int gdsp_cpsd_batch(const double *x, int64_t ldx, const double *y, int64_t ldy, int64_t y_rows,
-                    int64_t channels, int64_t n, double fs, int64_t nfft, int64_t pad,
-                    int64_t noverlap, const double *win_seg, const double *win_nfft,
-                    int scale_off, double *pxy, double *pxx, double *pyy, double *coh,
-                    double *freqs, int64_t *lp_out) {
-  if (!lp_out) return fail(GDSP_ERR_INVALID, "NULL pointer");
-  *lp_out = 0;
-  if (channels < 0 || n < 0 || y_rows < 0) return fail(GDSP_ERR_INVALID, "negative size");
-  if (n == 0) return GDSP_OK;
-  if (y_rows != 1 && y_rows != channels)
-    return fail(GDSP_ERR_UNEQUAL, "y is neither one row nor a row per channel");
-  if (nfft == 0) nfft = 256;
-  if (pad == 0) pad = nfft;
-  if (nfft < 0 || pad < 0) return fail(GDSP_ERR_INVALID, "negative NFFT/Pad");
-  if ((channels > 1 && ldx < n) || (y_rows > 1 && ldy < n))
-    return fail(GDSP_ERR_INVALID, "row stride below the channel length");
-  const int64_t lx = n < nfft ? nfft : n;  // dsputils.ZeroPadF(x, nfft) per channel
-  int64_t nsegs = 0;
-  STCHK(segment_count(lx, nfft, noverlap, &nsegs));
-  if (!freqs || (channels > 0 && (!x || !y || !pxy))) return fail(GDSP_ERR_INVALID, "NULL pointer");
-  const int64_t flen = pad > nfft ? pad : nfft;
-  const int64_t lp = pad / 2 + 1, hb = flen / 2 + 1;
-  if (channels == 0) {
-    (void)cpsd_norm_freqs(win_nfft, nfft, pad, fs, scale_off, freqs);
-    *lp_out = lp;
-    return GDSP_OK;
-  }
-  std::vector<double> hseg;
-  if (!win_seg) {
-    hseg.resize((size_t)flen);
-    hann_table(flen, hseg.data());
-    win_seg = hseg.data();
-  }
-  int dev = 0;
-  STCHK(current_device(&dev));
-  hipStream_t s = thread_stream(dev);
-  if (!s) return fail(GDSP_ERR_HIP, "stream creation failed");
-  const size_t rowb = (size_t)lx * sizeof(double);
-  const size_t abytes = (size_t)channels * (size_t)(4 * hb) * sizeof(double);
-  const size_t cl = (size_t)channels * (size_t)lp;
-  // outputs in one buffer: pxy (2 cl doubles), then pxx, pyy, coh where asked
-  double *const outs[3] = {pxx, pyy, coh};
-  size_t ndbl = 2 * cl;
-  for (double *o : outs) ndbl += o ? cl : 0;
-  DevBuf dx, dy, dw, dacc, dout;
-  STCHK(dx.alloc((size_t)channels * rowb, s, SLOT_IN));
-  STCHK(dy.alloc((size_t)y_rows * rowb, s, SLOT_CP_Y));
-  STCHK(dw.alloc((size_t)flen * sizeof(double), s, SLOT_AUX));
-  STCHK(dacc.alloc(abytes, s, SLOT_AUX2));
-  STCHK(dout.alloc(ndbl * sizeof(double), s, SLOT_CP_OUT));
-  double *px = (double *)dx.p, *py = (double *)dy.p, *po = (double *)dout.p;
-  double *dev_out[3] = {nullptr, nullptr, nullptr};
-  size_t off = 2 * cl;
-  for (int i = 0; i < 3; ++i)
-    if (outs[i]) {
-      dev_out[i] = po + off;
-      off += cl;
-    }
-  // rows of lx on the device, a short signal zero-padded (pwelch.go:97-99)
-  auto stage = [&](double *d, const double *h, int64_t rows, int64_t ld) -> int {
-    if (lx > n) HIPCHK(hipMemsetAsync(d, 0, (size_t)rows * rowb, s));
-    if (lx == n && (ld == n || rows == 1)) return copy_h2d(d, h, (size_t)rows * rowb, s);
-    for (int64_t c = 0; c < rows; ++c)
-      STCHK(copy_h2d(d + c * lx, h + c * ld, (size_t)n * sizeof(double), s));
-    return GDSP_OK;
-  };
-  auto queue = [&]() -> int {
-    STCHK(stage(px, x, channels, ldx));
-    STCHK(stage(py, y, y_rows, ldy));
-    STCHK(copy_h2d(dw.p, win_seg, (size_t)flen * sizeof(double), s));
-    HIPCHK(hipMemsetAsync(dacc.p, 0, abytes, s));
-    STCHK(gdsp_cpsd_batch_accumulate_device(px, lx, py, lx, y_rows, channels, lx, nfft, pad,
-                                            noverlap, 0, nsegs, (const double *)dw.p,
-                                            (double *)dacc.p, s));
-    return gdsp_cpsd_batch_finalize_device((const double *)dacc.p, channels, flen, nsegs, nfft,
-                                           pad, win_nfft, fs, scale_off, po, dev_out[0],
-                                           dev_out[1], dev_out[2], freqs, s);
-  };
-  const int st = queue();
-  if (st != GDSP_OK) {
-    (void)hipStreamSynchronize(s);  // queued copies still read the staging halves
-    return st;
-  }
-  STCHK(copy_d2h(pxy, po, 2 * cl * sizeof(double), s));
-  for (int i = 0; i < 3; ++i)
-    if (outs[i]) STCHK(copy_d2h(outs[i], dev_out[i], cl * sizeof(double), s));
-  *lp_out = lp;
-  return GDSP_OK;
 }
 
 static bool wav_format_ok(int audio_format, int bits) {

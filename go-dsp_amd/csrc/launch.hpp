@@ -1,5 +1,6 @@
 // launch.hpp — host launchers of the gfx950 kernels (fft_kernels.hip), used by
-// the C ABI layer (gdsp_api.hip). Internal to libgdspfft.
+// the C ABI layer (gdsp_api.hip; the Welch family's in welch.hip). Internal to
+// libgdspfft.
 #pragma once
 #ifndef __HIPCC_RTC__  // the device-side parts are also compiled by hipRTC (mixed_jit.cpp)
 #include <hip/hip_runtime.h>

@@ -45,20 +45,7 @@
 
 namespace {
 
-using gdsp_api::set_error;
-
-#define MHIPCHK(expr)                                                                  \
-  do {                                                                                 \
-    hipError_t e_ = (expr);                                                            \
-    if (e_ != hipSuccess)                                                              \
-      return set_error(GDSP_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(e_)); \
-  } while (0)
-
-#define MSTCHK(expr)              \
-  do {                            \
-    int s_ = (expr);              \
-    if (s_ != GDSP_OK) return s_; \
-  } while (0)
+using gdsp_api::fail;
 
 // ---- device set -------------------------------------------------------------
 
@@ -84,7 +71,7 @@ int validate(const int *devices, int ndev, int count, std::vector<int> &out) {
   for (int i = 0; i < ndev; ++i) {
     const int d = devices[i];
     if (d < 0 || d >= count)
-      return set_error(GDSP_ERR_INVALID, "device " + std::to_string(d) + " not visible (" +
+      return fail(GDSP_ERR_INVALID, "device " + std::to_string(d) + " not visible (" +
                                              std::to_string(count) + " devices)");
     out.push_back(d);
   }
@@ -119,8 +106,8 @@ void read_env_locked(int count) {
 int resolve(const int *devices, int ndev, std::vector<int> &out, bool *configured = nullptr) {
   const int count = visible_devices();
   if (configured) *configured = false;
-  if (count <= 0) return set_error(GDSP_ERR_NO_DEVICE, "no HIP device visible");
-  if (ndev < 0) return set_error(GDSP_ERR_INVALID, "negative device count");
+  if (count <= 0) return fail(GDSP_ERR_NO_DEVICE, "no HIP device visible");
+  if (ndev < 0) return fail(GDSP_ERR_INVALID, "negative device count");
   if (devices && ndev > 0) return validate(devices, ndev, count, out);
   {
     std::lock_guard<std::mutex> lk(g_set_mu);
@@ -132,7 +119,7 @@ int resolve(const int *devices, int ndev, std::vector<int> &out, bool *configure
     }
   }
   int cur = 0;
-  if (hipGetDevice(&cur) != hipSuccess) return set_error(GDSP_ERR_NO_DEVICE, "hipGetDevice failed");
+  if (hipGetDevice(&cur) != hipSuccess) return fail(GDSP_ERR_NO_DEVICE, "hipGetDevice failed");
   out.assign(1, cur);
   return GDSP_OK;
 }
@@ -174,7 +161,7 @@ class Pool {
             wp->th = std::thread([wp] { loop(wp); });
             wp->th.detach();
           } catch (...) {
-            return set_error(GDSP_ERR_NOMEM, "cannot start a device worker thread");
+            return fail(GDSP_ERR_NOMEM, "cannot start a device worker thread");
           }
           wp->key = key;
           it = ws_.emplace(key, std::move(w)).first;
@@ -207,12 +194,12 @@ class Pool {
         msg = w->msg;
       }
     }
-    if (st != GDSP_OK) return set_error(st, msg);
+    if (st != GDSP_OK) return fail(st, msg);
     if (!after) return GDSP_OK;
     try {
       return after();
     } catch (...) {  // nothing may throw past the C ABI
-      return set_error(GDSP_ERR_NOMEM, "exception in a multi-device call");
+      return fail(GDSP_ERR_NOMEM, "exception in a multi-device call");
     }
   }
 
@@ -241,7 +228,7 @@ class Pool {
       try {
         st = (*f)(idx);
       } catch (...) {  // nothing may throw past the C ABI
-        st = set_error(GDSP_ERR_NOMEM, "exception in a device worker");
+        st = fail(GDSP_ERR_NOMEM, "exception in a device worker");
       }
       const std::string msg = st == GDSP_OK ? std::string() : std::string(gdsp_last_error());
       lk.lock();
@@ -294,7 +281,7 @@ const Rccl &rccl() {
 }
 
 int nccl_fail(const Rccl &r, ncclResult_t e, const char *what) {
-  return set_error(GDSP_ERR_HIP, std::string(what) + ": " + r.error_string(e));
+  return fail(GDSP_ERR_HIP, std::string(what) + ": " + r.error_string(e));
 }
 
 // One clique per device list, built once (ncclCommInitAll) and kept until
@@ -327,10 +314,10 @@ int comms_for(const std::vector<int> &devs, std::vector<ncclComm_t> **out) {
   auto &mu = g_comms_mu;
   auto &cache = g_comms;
   const Rccl &r = rccl();
-  if (!r.why.empty()) return set_error(GDSP_ERR_UNSUPPORTED, r.why);
+  if (!r.why.empty()) return fail(GDSP_ERR_UNSUPPORTED, r.why);
   std::lock_guard<std::mutex> lk(mu);
   auto bad = g_comms_refused.find(devs);
-  if (bad != g_comms_refused.end()) return set_error(GDSP_ERR_UNSUPPORTED, bad->second.why);
+  if (bad != g_comms_refused.end()) return fail(GDSP_ERR_UNSUPPORTED, bad->second.why);
   auto it = cache.find(devs);
   if (it == cache.end()) {
     std::vector<ncclComm_t> c(devs.size());
@@ -404,20 +391,20 @@ bool multi_wanted(size_t bytes, int64_t units) {
 
 int fft_batch_multi(const void *x, size_t in_elem_bytes, double *out, int64_t n, int64_t batch,
                     bool inv, int load, const int *devices, int ndev) {
-  if (n < 0 || batch < 0) return set_error(GDSP_ERR_INVALID, "negative size");
+  if (n < 0 || batch < 0) return fail(GDSP_ERR_INVALID, "negative size");
   std::vector<int> devs;
-  MSTCHK(resolve(devices, ndev, devs));
-  if (batch == 0 || n == 0) return batch_on_current_device(x, in_elem_bytes, out, n, batch, inv, load);
-  if (!x || !out) return set_error(GDSP_ERR_INVALID, "NULL pointer");
+  STCHK(resolve(devices, ndev, devs));
+  if (batch == 0 || n == 0) return host_batch(x, in_elem_bytes, out, n, batch, inv, load);
+  if (!x || !out) return fail(GDSP_ERR_INVALID, "NULL pointer");
   const int parts = (int)std::min<int64_t>((int64_t)devs.size(), batch);
   ++g_batch_calls;
   const std::vector<int> used(devs.begin(), devs.begin() + parts);
   return Pool::get().run(used, [&](int i) -> int {
     int64_t lo, hi;
     shard(batch, parts, i, &lo, &hi);
-    MHIPCHK(hipSetDevice(devs[i]));
+    HIPCHK(hipSetDevice(devs[i]));
     const size_t row_in = (size_t)n * in_elem_bytes, row_out = (size_t)n * 2;
-    return batch_on_current_device((const char *)x + (size_t)lo * row_in, in_elem_bytes,
+    return host_batch((const char *)x + (size_t)lo * row_in, in_elem_bytes,
                                    out + (size_t)lo * row_out, n, hi - lo, inv, load);
   });
 }
@@ -442,32 +429,19 @@ int pwelch_multi(const double *x, int64_t n, double fs, int64_t nfft, int64_t pa
                  int64_t noverlap, const double *win_seg, const double *win_nfft, int scale_off,
                  double *pxx, double *freqs, int64_t *lp_out, const int *devices, int ndev) {
   // spectral/pwelch.go:74-145, segments sharded over devices
-  if (!lp_out) return set_error(GDSP_ERR_INVALID, "NULL pointer");
+  if (!lp_out) return fail(GDSP_ERR_INVALID, "NULL pointer");
   *lp_out = 0;
-  if (n < 0) return set_error(GDSP_ERR_INVALID, "negative size");
+  if (n < 0) return fail(GDSP_ERR_INVALID, "negative size");
   std::vector<int> devs;
-  MSTCHK(resolve(devices, ndev, devs));
+  STCHK(resolve(devices, ndev, devs));
   if (n == 0) return GDSP_OK;
-  if (nfft == 0) nfft = 256;
-  if (pad == 0) pad = nfft;
-  if (nfft < 0 || pad < 0) return set_error(GDSP_ERR_INVALID, "negative NFFT/Pad");
-  if (!x || !pxx || !freqs) return set_error(GDSP_ERR_INVALID, "NULL pointer");
-  const int64_t lx = n < nfft ? nfft : n;  // dsputils.ZeroPadF(x, nfft)
-  int64_t nsegs = 0;
-  MSTCHK(segments(lx, nfft, noverlap, &nsegs));
-  const int64_t flen = pad > nfft ? pad : nfft;
-  const int64_t lp = pad / 2 + 1;
-  std::vector<double> hseg, hnfft;
-  if (!win_seg) {
-    hseg.resize((size_t)flen);
-    hann(flen, hseg.data());
-    win_seg = hseg.data();
-  }
-  if (!win_nfft) {
-    hnfft.resize((size_t)nfft);
-    hann(nfft, hnfft.data());
-    win_nfft = hnfft.data();
-  }
+  if (!welch_defaults(&nfft, &pad)) return fail(GDSP_ERR_INVALID, "negative NFFT/Pad");
+  if (!x || !pxx || !freqs) return fail(GDSP_ERR_INVALID, "NULL pointer");
+  WelchShape w;
+  STCHK(welch_shape(n, nfft, pad, noverlap, &w));
+  const int64_t nsegs = w.nsegs, flen = w.flen;
+  std::vector<double> hseg;
+  win_seg = hann_or(win_seg, flen, hseg);
   std::vector<double> acc((size_t)flen, 0.0);
   if (nsegs > 0) {
     // the caller's current device is restored on every return path
@@ -495,32 +469,32 @@ int pwelch_multi(const double *x, int64_t n, double fs, int64_t nfft, int64_t pa
     // call-owned device buffer (a failing shard reports its own status and
     // message; the others return GDSP_OK and their work is dropped).
     auto accumulate = [&](int i) -> int {
-      MHIPCHK(hipSetDevice(devs[i]));
-      hipStream_t s = stream_for(devs[i]);
-      if (!s) return set_error(GDSP_ERR_HIP, "stream creation failed");
+      HIPCHK(hipSetDevice(devs[i]));
+      hipStream_t s = thread_stream(devs[i]);
+      if (!s) return fail(GDSP_ERR_HIP, "stream creation failed");
       streams[(size_t)i] = s;
       int64_t seg_lo, seg_hi, x_lo, x_hi;
       pwelch_shard(nsegs, nfft, noverlap, D, i, &seg_lo, &seg_hi, &x_lo, &x_hi);
-      void *dx = nullptr, *dw = nullptr;
+      DevBuf dx, dw;
       const int64_t len = x_hi - x_lo;
       CallBuf &a = dacc[(size_t)i];
       a.dev = devs[i];
-      MHIPCHK(hipMalloc(&a.p, (size_t)flen * sizeof(double)));
-      MSTCHK(scratch((size_t)(len > 0 ? len : 1) * sizeof(double), s, SCRATCH_SIGNAL, &dx));
-      MSTCHK(scratch((size_t)flen * sizeof(double), s, SCRATCH_WINDOW, &dw));
-      MHIPCHK(hipMemsetAsync(a.p, 0, (size_t)flen * sizeof(double), s));
+      HIPCHK(hipMalloc(&a.p, (size_t)flen * sizeof(double)));
+      STCHK(dx.alloc((size_t)(len > 0 ? len : 1) * sizeof(double), s, SLOT_IN));
+      STCHK(dw.alloc((size_t)flen * sizeof(double), s, SLOT_AUX));
+      HIPCHK(hipMemsetAsync(a.p, 0, (size_t)flen * sizeof(double), s));
       if (len > 0) {
         const int64_t have = (x_hi < n ? x_hi : n) - x_lo;  // past n: ZeroPadF's zeros
-        if (have < len) MHIPCHK(hipMemsetAsync(dx, 0, (size_t)len * sizeof(double), s));
-        if (have > 0) MSTCHK(h2d(dx, x + x_lo, (size_t)have * sizeof(double), s));
-        MSTCHK(h2d(dw, win_seg, (size_t)flen * sizeof(double), s));
-        MSTCHK(gdsp_pwelch_accumulate_device((const double *)dx, len, nfft, pad, noverlap, 0,
-                                             seg_hi - seg_lo, (const double *)dw,
-                                             (double *)a.p, s));
+        if (have < len) HIPCHK(hipMemsetAsync(dx.p, 0, (size_t)len * sizeof(double), s));
+        if (have > 0) STCHK(copy_h2d(dx.p, x + x_lo, (size_t)have * sizeof(double), s));
+        STCHK(copy_h2d(dw.p, win_seg, (size_t)flen * sizeof(double), s));
+        STCHK(gdsp_pwelch_accumulate_device((const double *)dx.p, len, nfft, pad, noverlap, 0,
+                                            seg_hi - seg_lo, (const double *)dw.p,
+                                            (double *)a.p, s));
       }
       if (use_rccl) return GDSP_OK;  // the reduce reads it on the same stream
       part[(size_t)i].resize((size_t)flen);
-      return d2h(part[(size_t)i].data(), a.p, (size_t)flen * sizeof(double), s);
+      return copy_d2h(part[(size_t)i].data(), a.p, (size_t)flen * sizeof(double), s);
     };
     // Phase 2, on the calling thread once every shard succeeded, still inside
     // the pool's call: one grouped RCCL reduce over the clique (a single
@@ -537,12 +511,12 @@ int pwelch_multi(const double *x, int64_t n, double fs, int64_t nfft, int64_t pa
         // the host and are summed there, and the call succeeds without
         // leaving the refusal as its last error
         for (int i = 0; i < D; ++i) {
-          MHIPCHK(hipSetDevice(devs[i]));
+          HIPCHK(hipSetDevice(devs[i]));
           part[(size_t)i].resize((size_t)flen);
-          MSTCHK(d2h(part[(size_t)i].data(), dacc[(size_t)i].p, (size_t)flen * sizeof(double),
+          STCHK(copy_d2h(part[(size_t)i].data(), dacc[(size_t)i].p, (size_t)flen * sizeof(double),
                      streams[(size_t)i]));
         }
-        return set_error(GDSP_OK, prev_error);
+        return fail(GDSP_OK, prev_error);
       }
       ncclResult_t e = r.group_start();
       if (e != ncclSuccess) return nccl_fail(r, e, "ncclGroupStart");
@@ -563,12 +537,12 @@ int pwelch_multi(const double *x, int64_t n, double fs, int64_t nfft, int64_t pa
         drop_comms(devs);
         return st;
       }
-      MHIPCHK(hipSetDevice(devs[0]));
+      HIPCHK(hipSetDevice(devs[0]));
       part[0].resize((size_t)flen);
-      MSTCHK(d2h(part[0].data(), dacc[0].p, (size_t)flen * sizeof(double), streams[0]));
+      STCHK(copy_d2h(part[0].data(), dacc[0].p, (size_t)flen * sizeof(double), streams[0]));
       for (int i = 1; i < D; ++i) {
-        MHIPCHK(hipSetDevice(devs[i]));
-        MHIPCHK(hipStreamSynchronize(streams[(size_t)i]));
+        HIPCHK(hipSetDevice(devs[i]));
+        HIPCHK(hipStreamSynchronize(streams[(size_t)i]));
       }
       reduced_by_rccl = true;
       return GDSP_OK;
@@ -577,7 +551,7 @@ int pwelch_multi(const double *x, int64_t n, double fs, int64_t nfft, int64_t pa
     // reduce, copy back): a concurrent call on an overlapping device set
     // queues behind it and never shares its accumulators, streams or clique;
     // one on a disjoint set runs beside it
-    MSTCHK(Pool::get().run(devs, accumulate, use_rccl ? std::function<int()>(reduce) : nullptr));
+    STCHK(Pool::get().run(devs, accumulate, use_rccl ? std::function<int()>(reduce) : nullptr));
     if (reduced_by_rccl) {
       acc.swap(part[0]);
       ++g_rccl_reduces;
@@ -587,9 +561,9 @@ int pwelch_multi(const double *x, int64_t n, double fs, int64_t nfft, int64_t pa
       ++g_host_reduces;
     }
   }
-  MSTCHK(gdsp_pwelch_finalize(acc.data(), flen, nsegs, nfft, pad, win_nfft, fs, scale_off, pxx,
+  STCHK(gdsp_pwelch_finalize(acc.data(), flen, nsegs, nfft, pad, win_nfft, fs, scale_off, pxx,
                               freqs));
-  *lp_out = lp;
+  *lp_out = w.lp;
   return GDSP_OK;
 }
 
@@ -601,11 +575,11 @@ int pwelch_multi(const double *x, int64_t n, double fs, int64_t nfft, int64_t pa
 extern "C" {
 
 int gdsp_set_devices(const int *devices, int ndev) {
-  if (ndev < 0 || (ndev > 0 && !devices)) return set_error(GDSP_ERR_INVALID, "bad device list");
+  if (ndev < 0 || (ndev > 0 && !devices)) return fail(GDSP_ERR_INVALID, "bad device list");
   const int count = visible_devices();
-  if (count <= 0) return set_error(GDSP_ERR_NO_DEVICE, "no HIP device visible");
+  if (count <= 0) return fail(GDSP_ERR_NO_DEVICE, "no HIP device visible");
   std::vector<int> v;
-  MSTCHK(validate(devices, ndev, count, v));
+  STCHK(validate(devices, ndev, count, v));
   std::lock_guard<std::mutex> lk(g_set_mu);
   g_set_env_read = true;  // an explicit set overrides GDSP_DEVICES
   g_set = v;
@@ -630,7 +604,7 @@ int gdsp_multi_stats(int64_t *batch_calls, int64_t *pwelch_calls, int64_t *rccl_
 
 int gdsp_batch_shard(int64_t batch, int ndev, int i, int64_t *lo, int64_t *hi) {
   if (batch < 0 || ndev <= 0 || i < 0 || i >= ndev || !lo || !hi)
-    return set_error(GDSP_ERR_INVALID, "bad argument");
+    return fail(GDSP_ERR_INVALID, "bad argument");
   shard(batch, ndev, i, lo, hi);
   return GDSP_OK;
 }
@@ -639,7 +613,7 @@ int gdsp_pwelch_shard(int64_t nsegs, int64_t nfft, int64_t noverlap, int ndev, i
                       int64_t *seg_lo, int64_t *seg_hi, int64_t *x_lo, int64_t *x_hi) {
   if (nsegs < 0 || nfft <= 0 || noverlap < 0 || noverlap >= nfft || ndev <= 0 || i < 0 ||
       i >= ndev || !seg_lo || !seg_hi || !x_lo || !x_hi)
-    return set_error(GDSP_ERR_INVALID, "bad argument");
+    return fail(GDSP_ERR_INVALID, "bad argument");
   pwelch_shard(nsegs, nfft, noverlap, ndev, i, seg_lo, seg_hi, x_lo, x_hi);
   return GDSP_OK;
 }

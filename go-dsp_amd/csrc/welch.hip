@@ -1,0 +1,623 @@
+// welch.hip — the Welch family of the C ABI (include/gdsp_fft.h): Pwelch, the
+// batched Pwelch over the channels of a planar batch, and the batched cross
+// spectra (Cpsd, coherence); with them spectral.Segment's count and the Hann
+// table. Host arithmetic only: the kernels are in pwelch_*.hip, cpsd_batch.hip
+// and the transform files, behind launch.hpp.
+#include <math.h>
+
+#include <string>
+#include <vector>
+
+#include "fft_device.hpp"
+#include "gdsp_fft.h"
+#include "launch.hpp"
+#include "api_internal.hpp"
+#include "plan.hpp"
+
+using gdsp::cd;
+using namespace gdsp_api;
+
+void gdsp_api::hann_table(int64_t L, double *r) {  // window/window.go:62-76
+  if (L <= 0) return;
+  if (L == 1) {
+    r[0] = 1;
+    return;
+  }
+  const int64_t N = L - 1;
+  const double coef = 2 * M_PI / (double)N;
+  for (int64_t i = 0; i <= N; ++i) r[i] = 0.5 * (1 - cos(coef * (double)i));
+}
+
+int gdsp_api::segment_count(int64_t lx, int64_t size, int64_t noverlap, int64_t *count) {
+  const int64_t stride = size - noverlap;  // spectral/spectral.go:22-33
+  if (lx == size) {
+    *count = 1;
+  } else if (lx > size) {
+    if (stride == 0) return fail(GDSP_ERR_DIVIDE_BY_ZERO, "integer divide by zero");
+    *count = (lx - size) / stride + 1;
+    if (*count < 0) return fail(GDSP_ERR_INVALID, "makeslice: len out of range");
+  } else {
+    *count = 0;
+  }
+  return GDSP_OK;
+}
+
+const double *gdsp_api::hann_or(const double *w, int64_t L, std::vector<double> &store) {
+  if (w) return w;
+  store.resize((size_t)L);
+  hann_table(L, store.data());
+  return store.data();
+}
+
+bool gdsp_api::welch_defaults(int64_t *nfft, int64_t *pad) {
+  if (*nfft == 0) *nfft = 256;
+  if (*pad == 0) *pad = *nfft;
+  return *nfft >= 0 && *pad >= 0;
+}
+
+int gdsp_api::welch_shape(int64_t n, int64_t nfft, int64_t pad, int64_t noverlap, WelchShape *w) {
+  w->lx = n < nfft ? nfft : n;
+  w->flen = pad > nfft ? pad : nfft;
+  w->lp = pad / 2 + 1;
+  return segment_count(w->lx, nfft, noverlap, &w->nsegs);
+}
+
+namespace {
+
+// The fused kernels address a pair's (or a wave's group of pairs') samples
+// with 32-bit offsets from one base; a very negative Noverlap (spectral.go:
+// 22-43 allows it) spreads the segments beyond that, so strides above 2^22
+// samples take the materialised paths, which index in 64 bits.
+constexpr int64_t kWelchMaxFusedStride = (int64_t)1 << 22;
+
+// the window's norm (spectral/pwelch.go:124-132; no window: Hann) and the
+// frequencies of the Pad / 2 + 1 bins (:138-142)
+double welch_norm(const double *win_nfft, int64_t nfft, double fs, int scale_off) {
+  std::vector<double> hw;
+  win_nfft = hann_or(win_nfft, nfft, hw);
+  double norm = 0;
+  for (int64_t i = 0; i < nfft; ++i) norm += win_nfft[i] * win_nfft[i];
+  if (!scale_off) norm *= fs;
+  return norm;
+}
+
+void welch_freqs(int64_t pad, double fs, double *freqs) {
+  const double coef = fs / (double)pad;
+  for (int64_t j = 0; j < pad / 2 + 1; ++j) freqs[j] = (double)j * coef;
+}
+
+// The partial sums of an accumulate call and the scratch of their reduction
+// into the accumulators in the fixed order: `rows` rows of F doubles
+// (launch_reduce_partials), or that per channel (launch_reduce_batch).
+struct Partials {
+  DevBuf part, red;
+  double *p() const { return (double *)part.p; }
+  int alloc(int64_t rows, int64_t F, hipStream_t s) {
+    STCHK(part.alloc((size_t)rows * (size_t)F * sizeof(double), s, SLOT_PW_PART));
+    return red.alloc((size_t)gdsp::reduce_scratch_doubles(rows, F) * sizeof(double), s,
+                     SLOT_PW_RED);
+  }
+  int reduce(int64_t rows, int64_t F, double *d_acc, hipStream_t s) {
+    HIPCHK(gdsp::launch_reduce_partials(p(), rows, F, d_acc, (double *)red.p, s));
+    return GDSP_OK;
+  }
+  int alloc_batch(int64_t channels, int64_t rows, int64_t F, hipStream_t s) {
+    STCHK(part.alloc((size_t)channels * (size_t)rows * (size_t)F * sizeof(double), s,
+                     SLOT_PW_PART));
+    return red.alloc(
+        (size_t)gdsp::reduce_batch_scratch_doubles(channels, rows, F) * sizeof(double), s,
+        SLOT_PW_RED);
+  }
+  int reduce_batch(int64_t channels, int64_t rows, int64_t F, double *d_acc, hipStream_t s) {
+    HIPCHK(gdsp::launch_reduce_batch(p(), channels, rows, F, d_acc, (double *)red.p, s));
+    return GDSP_OK;
+  }
+};
+
+// npairs packed segment pairs over at most `target` persistent workers, each a
+// contiguous range of ppw pairs
+void pair_workers(int64_t npairs, int64_t target, int64_t *ppw, int64_t *nworkers) {
+  if (target > npairs) target = npairs;
+  *ppw = (npairs + target - 1) / target;
+  *nworkers = (npairs + *ppw - 1) / *ppw;
+}
+
+// channels per launch of a batched kernel: the partials (per_channel doubles
+// each) within the materialised path's 512 MiB
+int64_t channels_per_launch(int64_t per_channel, int64_t channels) {
+  const int64_t cpl = ((int64_t)1 << 26) / per_channel;
+  return cpl < 1 ? 1 : (cpl > channels ? channels : cpl);
+}
+
+// Whether a batched kernel (its lengths: applies) serves transforms of flen
+// over this stride, unless the flag `off` is set. The flags are
+// gdsp_set_algorithm's: algo_flags() differs from them only inside a plan
+// build, and a build (the race included) runs exec_plan, never a Welch entry.
+bool batch_fused(int64_t flen, int64_t stride, bool (*applies)(int), unsigned off) {
+  return flen > 0 && is_pow2(flen) && applies(ilog2(flen)) && stride <= kWelchMaxFusedStride &&
+         !(gdsp::algo_flags() & off);
+}
+
+// The batched kernel (pwelch_batch.hip) serves the lengths of the wave
+// kernels; every other length and stride, and any shape under
+// GDSP_ALGO_NO_FUSED_PWELCH_BATCH, loops over the channels with
+// gdsp_pwelch_accumulate_device.
+bool pwelch_batch_fused(int64_t flen, int64_t stride) {
+  return batch_fused(flen, stride, gdsp::pwelch_batch_applies, GDSP_ALGO_NO_FUSED_PWELCH_BATCH);
+}
+
+// The fused kernel (cpsd_batch.hip) serves the lengths of the batched Pwelch;
+// every other length and stride, and any shape under GDSP_ALGO_NO_FUSED_CPSD,
+// runs the materialised form.
+bool cpsd_batch_fused(int64_t flen, int64_t stride) {
+  return batch_fused(flen, stride, gdsp::cpsd_batch_applies, GDSP_ALGO_NO_FUSED_CPSD);
+}
+
+// gdsp_pwelch_batch_fused / gdsp_cpsd_batch_fused: the predicate on a call's options
+int fused_answer(bool (*fused)(int64_t, int64_t), int64_t channels, int64_t n, int64_t nfft,
+                 int64_t pad, int64_t noverlap) {
+  if (channels < 0 || n < 0 || !welch_defaults(&nfft, &pad)) return 0;
+  return fused(pad > nfft ? pad : nfft, nfft - noverlap) ? 1 : 0;
+}
+
+}  // namespace
+
+extern "C" {
+
+int gdsp_segment_count(int64_t lx, int64_t size, int64_t noverlap, int64_t *count) {
+  if (!count) return fail(GDSP_ERR_INVALID, "NULL pointer");
+  return segment_count(lx, size, noverlap, count);
+}
+
+int gdsp_window_hann(int64_t L, double *out) {
+  if (L < 0) return fail(GDSP_ERR_INVALID, "negative size");
+  hann_table(L, out);
+  return GDSP_OK;
+}
+
+int gdsp_pwelch_accumulate_device(const double *d_x, int64_t n, int64_t nfft, int64_t pad,
+                                  int64_t noverlap, int64_t seg_begin, int64_t seg_end,
+                                  const double *d_win_seg, double *d_acc, void *stream) {
+  if (nfft <= 0 || pad <= 0 || seg_begin < 0 || seg_end < seg_begin)
+    return fail(GDSP_ERR_INVALID, "bad Pwelch geometry");
+  if (seg_end == seg_begin) return GDSP_OK;
+  const int64_t stride = nfft - noverlap;
+  if ((seg_end - 1) * stride + nfft > n && seg_end > 1)
+    return fail(GDSP_ERR_INVALID, "segments exceed the signal");
+  const int64_t flen = pad > nfft ? pad : nfft;
+  hipStream_t s = (hipStream_t)stream;  // NULL = the null stream
+  gdsp_plan *p = nullptr;
+  STCHK(get_plan(flen, &p));
+  const int64_t nseg = seg_end - seg_begin;
+  const bool fused = stride <= kWelchMaxFusedStride;
+  Partials pt;
+  if (fused && p->kind == KIND_LDS && gdsp::pwelch_wave_applies(p->log2n)) {
+    // 64 <= F <= 1024: wave-resident transforms, no workgroup barriers
+    // (pwelch_wave.hip), every wave a persistent worker over pair groups;
+    // F = 2048: two-wave workgroups
+    const bool half = 2 * noverlap == nfft && flen == nfft;
+    int64_t gpw = 0, nblk = 0, nrows = 0;
+    gdsp::pwelch_wave_geometry(p->log2n, half, nseg, &gpw, &nblk, &nrows);
+    STCHK(pt.alloc(nrows, flen, s));
+    HIPCHK(gdsp::launch_pwelch_wave(p->log2n, half, d_x, nfft, stride, seg_begin, seg_end, gpw,
+                                    nblk, d_win_seg, p->tw, pt.p(), s));
+    return pt.reduce(nrows, flen, d_acc, s);
+  }
+  // The other fused kernels: packed segment pairs, persistent workers over
+  // contiguous pair ranges (the 50 % overlap of consecutive pairs is re-read
+  // from L2), at most 2048 workers per workgroup slot: 512 / 1024 / 4096
+  // measured 2.86 / 2.81 / 2.77 against 2.76 ms for 2048 (BASELINE configs[4])
+  constexpr int64_t wmul = 2048;
+  const int64_t npairs = (nseg + 1) / 2;
+  int64_t ppw = 0, nworkers = 0;
+  auto workers = [&](int64_t target) -> int {
+    pair_workers(npairs, target, &ppw, &nworkers);
+    return pt.alloc(nworkers, flen, s);
+  };
+  if (fused && p->kind == KIND_LDS && p->log2n >= 4) {
+    STCHK(workers(wmul * (int64_t)gdsp::pwelch_workers_per_block(p->log2n)));
+    if (2 * noverlap == nfft && flen == nfft && p->log2n >= 5) {
+      // half overlap: each sample loaded once, window in LDS
+      HIPCHK(gdsp::launch_pwelch_half(p->log2n, d_x, seg_begin, seg_end, ppw, nworkers, d_win_seg,
+                                      p->tw, pt.p(), s));
+    } else if (p->log2n == 12 && flen == nfft) {
+      // any other overlap at 4096: the row kernel's structure without the carry
+      HIPCHK(gdsp::launch_pwelch_rowg4096(d_x, stride, seg_begin, seg_end, ppw, nworkers,
+                                          d_win_seg, p->tw, pt.p(), s));
+    } else {
+      HIPCHK(gdsp::launch_pwelch(p->log2n, d_x, nfft, stride, seg_begin, seg_end, ppw, nworkers,
+                                 d_win_seg, p->tw, pt.p(), s));
+    }
+    return pt.reduce(nworkers, flen, d_acc, s);
+  }
+  // the fused Pwelch on a compiled or runtime-compiled specialisation, on the
+  // Pwelch's own list where it has one (md_pw); 0 workers per block where its
+  // kernel cannot stage a pair this far apart (negative Noverlap)
+  const bool own = p->md_pw.n > 0 && !p->jit;
+  const gdsp::MixedDesc &pmd = own ? p->md_pw : p->md;
+  const int wpb_fixed =
+      !fused || p->kind != KIND_MIXED ? 0
+      : p->jit                        ? gdsp::jit_pw_tpw(p->jit, stride + nfft)
+                                      : gdsp::pwelch_fixed_workers_per_block(pmd, stride + nfft);
+  if (wpb_fixed > 0 && !(gdsp::algo_flags() & GDSP_ALGO_GENERIC_MIXED)) {
+    // fused path on a compiled specialisation (e.g. NFFT 1000, 3000)
+    STCHK(workers(wmul * (int64_t)wpb_fixed));
+    if (p->jit)
+      HIPCHK(gdsp::jit_launch_pwelch(p->jit, d_x, nfft, stride, seg_begin, seg_end, ppw, nworkers,
+                                     d_win_seg, p->tw, pt.p(), s));
+    else
+      HIPCHK(gdsp::launch_pwelch_fixed(pmd, d_x, nfft, stride, seg_begin, seg_end, ppw, nworkers,
+                                       d_win_seg, own ? p->tw_pw : p->tw, pt.p(), s));
+    return pt.reduce(nworkers, flen, d_acc, s);
+  }
+  if (fused && p->kind == KIND_MIXED && p->md_gen.npass >= 2) {
+    // fused mixed-radix path (smooth NFFT / Pad up to 4096)
+    STCHK(workers(wmul));
+    HIPCHK(gdsp::launch_pwelch_mixed(p->md_gen, d_x, nfft, stride, seg_begin, seg_end, ppw,
+                                     nworkers, d_win_seg, p->tw_gen, pt.p(), s));
+    return pt.reduce(nworkers, flen, d_acc, s);
+  }
+  // materialised path (lengths without a fused kernel): packed segment pairs
+  // as complex rows, the batched FFT of the plan, per-bin partial power sums,
+  // deterministic reduction into acc
+  int64_t rows = ((int64_t)1 << 25) / flen;  // 512 MiB of rows per chunk
+  constexpr int64_t kRpp = 64;
+  if (rows < 1) rows = 1;
+  if (rows > 65535 * kRpp) rows = 65535 * kRpp;  // partial-sum grid limit
+  if (rows > npairs) rows = npairs;
+  DevBuf buf;
+  STCHK(buf.alloc((size_t)rows * (size_t)flen * sizeof(cd), s, SLOT_PW_BUF));
+  STCHK(pt.alloc((rows + kRpp - 1) / kRpp, flen, s));
+  for (int64_t r0 = 0; r0 < npairs; r0 += rows) {
+    const int64_t nr = (npairs - r0) < rows ? (npairs - r0) : rows;
+    HIPCHK(gdsp::launch_segments_to_complex(d_x, nfft, flen, stride, seg_begin + 2 * r0, seg_end,
+                                            nr, d_win_seg, (cd *)buf.p, s));
+    STCHK(exec_plan(p, buf.p, (cd *)buf.p, nr, false, gdsp::LOAD_COMPLEX, s));
+    HIPCHK(gdsp::launch_power_partials((const cd *)buf.p, nr, flen, kRpp, pt.p(), s));
+    STCHK(pt.reduce((nr + kRpp - 1) / kRpp, flen, d_acc, s));
+  }
+  return GDSP_OK;
+}
+
+int gdsp_pwelch_finalize(const double *acc, int64_t flen, int64_t nsegs, int64_t nfft,
+                         int64_t pad, const double *win_nfft, double fs, int scale_off,
+                         double *pxx, double *freqs) {
+  // spectral/pwelch.go:113-142
+  if (flen <= 0 || nfft <= 0 || pad <= 0 || !pxx || !freqs)
+    return fail(GDSP_ERR_INVALID, "bad argument");
+  const int64_t lp = pad / 2 + 1;
+  const double norm = welch_norm(win_nfft, nfft, fs, scale_off);
+  for (int64_t j = 0; j < lp; ++j) {
+    double d = 0.0;
+    if (nsegs > 0) {
+      d = 0.5 * (acc[j] + acc[(flen - j) % flen]) / (double)nsegs;
+      if (j > 0 && j < lp - 1) d *= 2;
+    }
+    pxx[j] = d / norm;
+  }
+  welch_freqs(pad, fs, freqs);
+  return GDSP_OK;
+}
+
+int gdsp_pwelch(const double *x, int64_t n, double fs, int64_t nfft, int64_t pad,
+                int64_t noverlap, const double *win_seg, const double *win_nfft, int scale_off,
+                double *pxx, double *freqs, int64_t *lp_out) {
+  // spectral/pwelch.go:74-145
+  if (!lp_out) return fail(GDSP_ERR_INVALID, "NULL pointer");
+  *lp_out = 0;
+  if (n < 0) return fail(GDSP_ERR_INVALID, "negative size");
+  if (n == 0) return GDSP_OK;
+  if (!welch_defaults(&nfft, &pad)) return fail(GDSP_ERR_INVALID, "negative NFFT/Pad");
+  WelchShape w;
+  STCHK(welch_shape(n, nfft, pad, noverlap, &w));
+  std::vector<double> hseg;
+  win_seg = hann_or(win_seg, w.flen, hseg);
+  if (w.nsegs >= 2 && multi_wanted((size_t)n * sizeof(double), w.nsegs))
+    return pwelch_multi(x, n, fs, nfft, pad, noverlap, win_seg, win_nfft, scale_off, pxx, freqs,
+                        lp_out, nullptr, 0);
+  std::vector<double> acc((size_t)w.flen, 0.0);
+  if (w.nsegs > 0) {
+    int dev = 0;
+    STCHK(current_device(&dev));
+    hipStream_t s = thread_stream(dev);
+    if (!s) return fail(GDSP_ERR_HIP, "stream creation failed");
+    const size_t fbytes = (size_t)w.flen * sizeof(double);
+    DevBuf dx, dw, dacc;
+    STCHK(dx.alloc((size_t)w.lx * sizeof(double), s, SLOT_IN));
+    STCHK(dw.alloc(fbytes, s, SLOT_AUX));
+    STCHK(dacc.alloc(fbytes, s, SLOT_AUX2));
+    STCHK(run_queued(s, [&]() -> int {
+      STCHK(stage_rows((double *)dx.p, x, 1, n, n, w.lx, s));
+      STCHK(copy_h2d(dw.p, win_seg, fbytes, s));
+      HIPCHK(hipMemsetAsync(dacc.p, 0, fbytes, s));
+      return gdsp_pwelch_accumulate_device((const double *)dx.p, w.lx, nfft, pad, noverlap, 0,
+                                           w.nsegs, (const double *)dw.p, (double *)dacc.p, s);
+    }));
+    STCHK(copy_d2h(acc.data(), dacc.p, fbytes, s));
+  }
+  STCHK(gdsp_pwelch_finalize(acc.data(), w.flen, w.nsegs, nfft, pad, win_nfft, fs, scale_off, pxx,
+                             freqs));
+  *lp_out = w.lp;
+  return GDSP_OK;
+}
+
+// ---- batched Pwelch: the channels of a planar batch in one call ---------------
+
+int gdsp_pwelch_batch_fused(int64_t channels, int64_t n, int64_t nfft, int64_t pad,
+                            int64_t noverlap) {
+  return fused_answer(pwelch_batch_fused, channels, n, nfft, pad, noverlap);
+}
+
+int gdsp_pwelch_batch_accumulate_device(const double *d_x, int64_t channels, int64_t n,
+                                        int64_t ldx, int64_t nfft, int64_t pad, int64_t noverlap,
+                                        int64_t seg_begin, int64_t seg_end,
+                                        const double *d_win_seg, double *d_acc, void *stream) {
+  if (nfft <= 0 || pad <= 0 || seg_begin < 0 || seg_end < seg_begin)
+    return fail(GDSP_ERR_INVALID, "bad Pwelch geometry");
+  if (channels < 0 || n < 0 || (channels > 1 && ldx < n))
+    return fail(GDSP_ERR_INVALID, "bad batch geometry");
+  if (channels == 0 || seg_end == seg_begin) return GDSP_OK;
+  if (!d_x || !d_win_seg || !d_acc) return fail(GDSP_ERR_INVALID, "NULL pointer");
+  const int64_t stride = nfft - noverlap;
+  if ((seg_end - 1) * stride + nfft > n && seg_end > 1)
+    return fail(GDSP_ERR_INVALID, "segments exceed the signal");
+  const int64_t flen = pad > nfft ? pad : nfft;
+  hipStream_t s = (hipStream_t)stream;
+  gdsp_plan *p = nullptr;
+  if (pwelch_batch_fused(flen, stride)) STCHK(get_plan(flen, &p));
+  if (!p || p->kind != KIND_LDS) {
+    for (int64_t c = 0; c < channels; ++c)
+      STCHK(gdsp_pwelch_accumulate_device(d_x + c * ldx, n, nfft, pad, noverlap, seg_begin,
+                                          seg_end, d_win_seg, d_acc + c * flen, stream));
+    return GDSP_OK;
+  }
+  const bool half = 2 * noverlap == nfft && flen == nfft;
+  int64_t wpc = 0, gpw = 0, rows = 0;
+  gdsp::pwelch_batch_geometry(p->log2n, half, channels, seg_end - seg_begin, &wpc, &gpw, &rows);
+  const int64_t cpl = channels_per_launch(rows * flen, channels);
+  Partials pt;
+  STCHK(pt.alloc_batch(cpl, rows, flen, s));
+  for (int64_t c0 = 0; c0 < channels; c0 += cpl) {
+    const int64_t nc = channels - c0 < cpl ? channels - c0 : cpl;
+    HIPCHK(gdsp::launch_pwelch_batch(p->log2n, half, d_x + c0 * ldx, ldx, nc, wpc, nfft, stride,
+                                     seg_begin, seg_end, gpw, d_win_seg, p->tw, pt.p(), s));
+    STCHK(pt.reduce_batch(nc, rows, flen, d_acc + c0 * flen, s));
+  }
+  return GDSP_OK;
+}
+
+int gdsp_pwelch_batch_finalize_device(const double *d_acc, int64_t channels, int64_t flen,
+                                      int64_t nsegs, int64_t nfft, int64_t pad,
+                                      const double *win_nfft, double fs, int scale_off,
+                                      double *d_pxx, double *freqs, void *stream) {
+  if (channels < 0 || flen <= 0 || nfft <= 0 || pad <= 0 || nsegs < 0)
+    return fail(GDSP_ERR_INVALID, "bad argument");
+  if (channels > 0 && (!d_acc || !d_pxx)) return fail(GDSP_ERR_INVALID, "NULL pointer");
+  const int64_t lp = pad / 2 + 1;
+  if (lp > flen) return fail(GDSP_ERR_INVALID, "accumulators shorter than Pad / 2 + 1");
+  const double norm = welch_norm(win_nfft, nfft, fs, scale_off);
+  if (freqs) welch_freqs(pad, fs, freqs);
+  if (channels == 0) return GDSP_OK;
+  HIPCHK(gdsp::launch_pwelch_finalize(d_acc, channels, flen, lp, nsegs, norm, d_pxx,
+                                      (hipStream_t)stream));
+  return GDSP_OK;
+}
+
+int gdsp_pwelch_batch(const double *x, int64_t channels, int64_t n, int64_t ldx, double fs,
+                      int64_t nfft, int64_t pad, int64_t noverlap, const double *win_seg,
+                      const double *win_nfft, int scale_off, double *pxx, double *freqs,
+                      int64_t *lp_out) {
+  if (!lp_out) return fail(GDSP_ERR_INVALID, "NULL pointer");
+  *lp_out = 0;
+  if (channels < 0 || n < 0) return fail(GDSP_ERR_INVALID, "negative size");
+  if (n == 0) return GDSP_OK;
+  if (!welch_defaults(&nfft, &pad)) return fail(GDSP_ERR_INVALID, "negative NFFT/Pad");
+  if (channels > 1 && ldx < n) return fail(GDSP_ERR_INVALID, "ldx below the channel length");
+  WelchShape w;
+  STCHK(welch_shape(n, nfft, pad, noverlap, &w));
+  if (!freqs || (channels > 0 && (!x || !pxx))) return fail(GDSP_ERR_INVALID, "NULL pointer");
+  if (channels == 0) {
+    welch_freqs(pad, fs, freqs);
+    *lp_out = w.lp;
+    return GDSP_OK;
+  }
+  std::vector<double> hseg, hnfft;
+  win_seg = hann_or(win_seg, w.flen, hseg);
+  win_nfft = hann_or(win_nfft, nfft, hnfft);  // once for every channel's finalisation
+  std::vector<double> acc((size_t)channels * (size_t)w.flen, 0.0);
+  if (w.nsegs > 0) {
+    int dev = 0;
+    STCHK(current_device(&dev));
+    hipStream_t s = thread_stream(dev);
+    if (!s) return fail(GDSP_ERR_HIP, "stream creation failed");
+    const size_t abytes = acc.size() * sizeof(double);
+    DevBuf dx, dw, dacc;
+    STCHK(dx.alloc((size_t)channels * (size_t)w.lx * sizeof(double), s, SLOT_IN));
+    STCHK(dw.alloc((size_t)w.flen * sizeof(double), s, SLOT_AUX));
+    STCHK(dacc.alloc(abytes, s, SLOT_AUX2));
+    STCHK(run_queued(s, [&]() -> int {
+      STCHK(stage_rows((double *)dx.p, x, channels, n, ldx, w.lx, s));
+      STCHK(copy_h2d(dw.p, win_seg, (size_t)w.flen * sizeof(double), s));
+      HIPCHK(hipMemsetAsync(dacc.p, 0, abytes, s));
+      return gdsp_pwelch_batch_accumulate_device((const double *)dx.p, channels, w.lx, w.lx, nfft,
+                                                 pad, noverlap, 0, w.nsegs, (const double *)dw.p,
+                                                 (double *)dacc.p, s);
+    }));
+    STCHK(copy_d2h(acc.data(), dacc.p, abytes, s));
+  }
+  for (int64_t c = 0; c < channels; ++c)
+    STCHK(gdsp_pwelch_finalize(acc.data() + c * w.flen, w.flen, w.nsegs, nfft, pad, win_nfft, fs,
+                               scale_off, pxx + c * w.lp, freqs));
+  *lp_out = w.lp;
+  return GDSP_OK;
+}
+
+// ---- batched cross spectra: Cpsd and coherence of x channels against y --------
+
+int gdsp_cpsd_batch_fused(int64_t channels, int64_t n, int64_t nfft, int64_t pad,
+                          int64_t noverlap) {
+  return fused_answer(cpsd_batch_fused, channels, n, nfft, pad, noverlap);
+}
+
+int gdsp_cpsd_batch_accumulate_device(const double *d_x, int64_t ldx, const double *d_y,
+                                      int64_t ldy, int64_t y_rows, int64_t channels, int64_t n,
+                                      int64_t nfft, int64_t pad, int64_t noverlap,
+                                      int64_t seg_begin, int64_t seg_end,
+                                      const double *d_win_seg, double *d_acc, void *stream) {
+  if (nfft <= 0 || pad <= 0 || seg_begin < 0 || seg_end < seg_begin)
+    return fail(GDSP_ERR_INVALID, "bad Cpsd geometry");
+  if (channels < 0 || n < 0 || y_rows < 0 || (channels > 1 && ldx < n) || (y_rows > 1 && ldy < n))
+    return fail(GDSP_ERR_INVALID, "bad batch geometry");
+  if (y_rows != 1 && y_rows != channels)
+    return fail(GDSP_ERR_UNEQUAL, "y is neither one row nor a row per channel");
+  const int64_t stride = nfft - noverlap;
+  // Segment divides by the stride only where there is more than one segment
+  if (stride == 0 && seg_end > 1) return fail(GDSP_ERR_DIVIDE_BY_ZERO, "integer divide by zero");
+  if (channels == 0 || seg_end == seg_begin) return GDSP_OK;
+  if (!d_x || !d_y || !d_win_seg || !d_acc) return fail(GDSP_ERR_INVALID, "NULL pointer");
+  // a negative stride (Noverlap > NFFT) leaves at most segment 0 (Segment)
+  if ((seg_end - 1) * stride + nfft > n || (stride < 0 && seg_end > 1))
+    return fail(GDSP_ERR_INVALID, "segments exceed the signal");
+  const int64_t flen = pad > nfft ? pad : nfft;
+  const int64_t hb = flen / 2 + 1, nseg = seg_end - seg_begin;
+  const int64_t ldyk = y_rows == 1 ? 0 : ldy;  // the kernels' y row stride
+  hipStream_t s = (hipStream_t)stream;
+  gdsp_plan *p = nullptr;
+  STCHK(get_plan(flen, &p));
+  Partials pt;
+  // get_plan builds a power of 2 up to 2^14 as KIND_LDS under every flag set
+  // (build_plan, plan.hip), so gdsp_cpsd_batch_fused's answer holds here; the
+  // kind is checked because the kernel reads that plan's twiddle table
+  if (cpsd_batch_fused(flen, stride) && p->kind == KIND_LDS) {
+    int64_t wpc = 0, gpw = 0, rows = 0;
+    gdsp::cpsd_batch_geometry(p->log2n, channels, nseg, &wpc, &gpw, &rows);
+    const int64_t cpl = channels_per_launch(rows * 4 * hb, channels);
+    STCHK(pt.alloc_batch(cpl, rows, 4 * hb, s));
+    for (int64_t c0 = 0; c0 < channels; c0 += cpl) {
+      const int64_t nc = channels - c0 < cpl ? channels - c0 : cpl;
+      HIPCHK(gdsp::launch_cpsd_batch(p->log2n, d_x + c0 * ldx, ldx, d_y + c0 * ldyk, ldyk, nc, wpc,
+                                     nfft, stride, seg_begin, seg_end, gpw, d_win_seg, p->tw,
+                                     pt.p(), s));
+      STCHK(pt.reduce_batch(nc, rows, 4 * hb, d_acc + c0 * 4 * hb, s));
+    }
+    return GDSP_OK;
+  }
+  // materialised form: chunks of at most 512 MiB of complex rows, whole
+  // channels where a channel's segments fit, else one channel's segments in
+  // runs; parts of kRpp rows, reduced in the fixed order
+  constexpr int64_t kRpp = 64;
+  int64_t maxrows = ((int64_t)1 << 25) / flen;
+  if (maxrows < 1) maxrows = 1;
+  const int64_t ns_max = nseg < maxrows ? nseg : maxrows;  // segments per run
+  int64_t cpl = maxrows / ns_max;                           // channels per launch
+  if (cpl > channels) cpl = channels;
+  DevBuf buf, bal;
+  STCHK(buf.alloc((size_t)cpl * (size_t)ns_max * (size_t)flen * sizeof(cd), s, SLOT_PW_BUF));
+  STCHK(bal.alloc((size_t)cpl * (size_t)ns_max * sizeof(double), s, SLOT_CP_BAL));
+  double *alpha = (double *)bal.p;  // a power of 2 per row (cpsd_batch.hip, Balance)
+  STCHK(pt.alloc_batch(cpl, (ns_max + kRpp - 1) / kRpp, 4 * hb, s));
+  for (int64_t c0 = 0; c0 < channels; c0 += cpl) {
+    const int64_t nc = channels - c0 < cpl ? channels - c0 : cpl;
+    for (int64_t j0 = 0; j0 < nseg; j0 += ns_max) {
+      const int64_t ns = nseg - j0 < ns_max ? nseg - j0 : ns_max;
+      HIPCHK(gdsp::launch_cpsd_balance(d_x + c0 * ldx, ldx, d_y + c0 * ldyk, ldyk, nc, ns, nfft,
+                                       stride, seg_begin + j0, d_win_seg, alpha, s));
+      HIPCHK(gdsp::launch_cpsd_gather(d_x + c0 * ldx, ldx, d_y + c0 * ldyk, ldyk, nc, ns, nfft,
+                                      flen, stride, seg_begin + j0, d_win_seg, alpha,
+                                      (cd *)buf.p, s));
+      STCHK(exec_plan(p, buf.p, (cd *)buf.p, nc * ns, false, gdsp::LOAD_COMPLEX, s));
+      HIPCHK(gdsp::launch_cpsd_partials((const cd *)buf.p, nc, ns, flen, kRpp, alpha, pt.p(), s));
+      STCHK(pt.reduce_batch(nc, (ns + kRpp - 1) / kRpp, 4 * hb, d_acc + c0 * 4 * hb, s));
+    }
+  }
+  return GDSP_OK;
+}
+
+int gdsp_cpsd_batch_finalize_device(const double *d_acc, int64_t channels, int64_t flen,
+                                    int64_t nsegs, int64_t nfft, int64_t pad,
+                                    const double *win_nfft, double fs, int scale_off,
+                                    void *d_pxy, double *d_pxx, double *d_pyy, double *d_coh,
+                                    double *freqs, void *stream) {
+  if (channels < 0 || flen <= 0 || nfft <= 0 || pad <= 0 || nsegs < 0)
+    return fail(GDSP_ERR_INVALID, "bad argument");
+  if (channels > 0 && !d_acc) return fail(GDSP_ERR_INVALID, "NULL pointer");
+  const int64_t lp = pad / 2 + 1, hb = flen / 2 + 1;
+  if (lp > hb) return fail(GDSP_ERR_INVALID, "accumulators shorter than Pad / 2 + 1");
+  const double norm = welch_norm(win_nfft, nfft, fs, scale_off);
+  if (freqs) welch_freqs(pad, fs, freqs);
+  if (channels == 0 || (!d_pxy && !d_pxx && !d_pyy && !d_coh)) return GDSP_OK;
+  HIPCHK(gdsp::launch_cpsd_finalize(d_acc, channels, hb, lp, nsegs, norm, (cd *)d_pxy, d_pxx,
+                                    d_pyy, d_coh, (hipStream_t)stream));
+  return GDSP_OK;
+}
+
+int gdsp_cpsd_batch(const double *x, int64_t ldx, const double *y, int64_t ldy, int64_t y_rows,
+                    int64_t channels, int64_t n, double fs, int64_t nfft, int64_t pad,
+                    int64_t noverlap, const double *win_seg, const double *win_nfft,
+                    int scale_off, double *pxy, double *pxx, double *pyy, double *coh,
+                    double *freqs, int64_t *lp_out) {
+  if (!lp_out) return fail(GDSP_ERR_INVALID, "NULL pointer");
+  *lp_out = 0;
+  if (channels < 0 || n < 0 || y_rows < 0) return fail(GDSP_ERR_INVALID, "negative size");
+  if (n == 0) return GDSP_OK;
+  if (y_rows != 1 && y_rows != channels)
+    return fail(GDSP_ERR_UNEQUAL, "y is neither one row nor a row per channel");
+  if (!welch_defaults(&nfft, &pad)) return fail(GDSP_ERR_INVALID, "negative NFFT/Pad");
+  if ((channels > 1 && ldx < n) || (y_rows > 1 && ldy < n))
+    return fail(GDSP_ERR_INVALID, "row stride below the channel length");
+  WelchShape w;
+  STCHK(welch_shape(n, nfft, pad, noverlap, &w));
+  if (!freqs || (channels > 0 && (!x || !y || !pxy))) return fail(GDSP_ERR_INVALID, "NULL pointer");
+  const int64_t lx = w.lx, lp = w.lp, hb = w.flen / 2 + 1;
+  if (channels == 0) {
+    welch_freqs(pad, fs, freqs);
+    *lp_out = lp;
+    return GDSP_OK;
+  }
+  std::vector<double> hseg;
+  win_seg = hann_or(win_seg, w.flen, hseg);
+  int dev = 0;
+  STCHK(current_device(&dev));
+  hipStream_t s = thread_stream(dev);
+  if (!s) return fail(GDSP_ERR_HIP, "stream creation failed");
+  const size_t rowb = (size_t)lx * sizeof(double);
+  const size_t abytes = (size_t)channels * (size_t)(4 * hb) * sizeof(double);
+  const size_t cl = (size_t)channels * (size_t)lp;
+  // outputs in one buffer: pxy (2 cl doubles), then pxx, pyy, coh where asked
+  double *const outs[3] = {pxx, pyy, coh};
+  size_t ndbl = 2 * cl;
+  for (double *o : outs) ndbl += o ? cl : 0;
+  DevBuf dx, dy, dw, dacc, dout;
+  STCHK(dx.alloc((size_t)channels * rowb, s, SLOT_IN));
+  STCHK(dy.alloc((size_t)y_rows * rowb, s, SLOT_CP_Y));
+  STCHK(dw.alloc((size_t)w.flen * sizeof(double), s, SLOT_AUX));
+  STCHK(dacc.alloc(abytes, s, SLOT_AUX2));
+  STCHK(dout.alloc(ndbl * sizeof(double), s, SLOT_CP_OUT));
+  double *px = (double *)dx.p, *py = (double *)dy.p, *po = (double *)dout.p;
+  double *dev_out[3] = {nullptr, nullptr, nullptr};
+  size_t off = 2 * cl;
+  for (int i = 0; i < 3; ++i)
+    if (outs[i]) {
+      dev_out[i] = po + off;
+      off += cl;
+    }
+  STCHK(run_queued(s, [&]() -> int {
+    STCHK(stage_rows(px, x, channels, n, ldx, lx, s));
+    STCHK(stage_rows(py, y, y_rows, n, ldy, lx, s));
+    STCHK(copy_h2d(dw.p, win_seg, (size_t)w.flen * sizeof(double), s));
+    HIPCHK(hipMemsetAsync(dacc.p, 0, abytes, s));
+    STCHK(gdsp_cpsd_batch_accumulate_device(px, lx, py, lx, y_rows, channels, lx, nfft, pad,
+                                            noverlap, 0, w.nsegs, (const double *)dw.p,
+                                            (double *)dacc.p, s));
+    return gdsp_cpsd_batch_finalize_device((const double *)dacc.p, channels, w.flen, w.nsegs, nfft,
+                                           pad, win_nfft, fs, scale_off, po, dev_out[0],
+                                           dev_out[1], dev_out[2], freqs, s);
+  }));
+  STCHK(copy_d2h(pxy, po, 2 * cl * sizeof(double), s));
+  for (int i = 0; i < 3; ++i)
+    if (outs[i]) STCHK(copy_d2h(outs[i], dev_out[i], cl * sizeof(double), s));
+  *lp_out = lp;
+  return GDSP_OK;
+}
+
+}  // extern "C"

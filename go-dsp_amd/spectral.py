@@ -53,22 +53,38 @@ def resolve_options(o: Optional[PwelchOptions]):
     return nfft, pad, o.Noverlap, wf, not o.Scale_off
 
 
+def _welch_args(o: Optional[PwelchOptions]):
+    """(nfft, pad, noverlap, win_seg, win_nfft, lp, scale_off) of a Welch call:
+    the resolved options, the window at max(pad, nfft) and at nfft, Pad / 2 + 1
+    and the C ABI's scale_off. Callers return on an empty input before this."""
+    nfft, pad, noverlap, wf, scaling = resolve_options(o)
+    win_seg = np.ascontiguousarray(wf(max(pad, nfft)), dtype=np.float64)
+    win_nfft = np.ascontiguousarray(wf(nfft), dtype=np.float64)
+    return nfft, pad, noverlap, win_seg, win_nfft, pad // 2 + 1, int(not scaling)
+
+
 def Pwelch(x, Fs: float, o: Optional[PwelchOptions]):
     """spectral.Pwelch — spectral/pwelch.go:74-145. Returns (Pxx, freqs)."""
     x = np.ascontiguousarray(np.asarray(x, dtype=np.float64).reshape(-1))
     if x.size == 0:
         return np.zeros(0), np.zeros(0)
-    nfft, pad, noverlap, wf, scaling = resolve_options(o)
-    flen = max(pad, nfft)
-    win_seg = np.ascontiguousarray(wf(flen), dtype=np.float64)
-    win_nfft = np.ascontiguousarray(wf(nfft), dtype=np.float64)
-    lp = pad // 2 + 1
+    nfft, pad, noverlap, win_seg, win_nfft, lp, scale_off = _welch_args(o)
     pxx = np.empty(lp, np.float64)
     freqs = np.empty(lp, np.float64)
     lpo = _lib._I64(0)
     check(lib().gdsp_pwelch(_p(x), x.size, float(Fs), nfft, pad, noverlap, _p(win_seg),
-                            _p(win_nfft), int(not scaling), _p(pxx), _p(freqs), lpo), "Pwelch")
+                            _p(win_nfft), scale_off, _p(pxx), _p(freqs), lpo), "Pwelch")
     return pxx[:lpo.value], freqs[:lpo.value]
+
+
+def _rows(rows):
+    """A (channels, n) float64 array of equal-length rows, or the ragged panic."""
+    if isinstance(rows, np.ndarray) and rows.ndim == 2:
+        return np.ascontiguousarray(rows, dtype=np.float64)
+    rs = [np.asarray(r, dtype=np.float64).reshape(-1) for r in rows]
+    if any(r.size != rs[0].size for r in rs):
+        raise Panic(_lib.GDSP_ERR_RAGGED, "ragged input array")
+    return np.ascontiguousarray(rs, dtype=np.float64).reshape(len(rs), rs[0].size if rs else 0)
 
 
 def pwelch_batch_fused(channels: int, n: int, nfft: int = 0, pad: int = 0,
@@ -83,26 +99,16 @@ def PwelchBatch(rows, Fs: float, o: Optional[PwelchOptions]):
     """spectral.Pwelch of every row of `rows` (equal lengths: the channels of
     a recording) in one call (gdsp_pwelch_batch). Returns (Pxx[channels, lp],
     freqs); row c equals Pwelch(rows[c], Fs, o)."""
-    if isinstance(rows, np.ndarray) and rows.ndim == 2:
-        x = np.ascontiguousarray(rows, dtype=np.float64)
-    else:
-        rs = [np.asarray(r, dtype=np.float64).reshape(-1) for r in rows]
-        if any(r.size != rs[0].size for r in rs):
-            raise Panic(_lib.GDSP_ERR_RAGGED, "ragged input array")
-        x = np.ascontiguousarray(rs, dtype=np.float64).reshape(len(rs), rs[0].size if rs else 0)
+    x = _rows(rows)
     channels, n = x.shape
     if n == 0:  # pwelch.go:75-77, before the options are looked at
         return np.zeros((channels, 0)), np.zeros(0)
-    nfft, pad, noverlap, wf, scaling = resolve_options(o)
-    flen = max(pad, nfft)
-    win_seg = np.ascontiguousarray(wf(flen), dtype=np.float64)
-    win_nfft = np.ascontiguousarray(wf(nfft), dtype=np.float64)
-    lp = pad // 2 + 1
+    nfft, pad, noverlap, win_seg, win_nfft, lp, scale_off = _welch_args(o)
     pxx = np.empty((channels, lp), np.float64)
     freqs = np.empty(lp, np.float64)
     lpo = _lib._I64(0)
     check(lib().gdsp_pwelch_batch(_p(x), channels, n, n, float(Fs), nfft, pad, noverlap,
-                                  _p(win_seg), _p(win_nfft), int(not scaling), _p(pxx),
+                                  _p(win_seg), _p(win_nfft), scale_off, _p(pxx),
                                   _p(freqs), lpo), "PwelchBatch")
     return pxx, freqs
 
@@ -123,16 +129,6 @@ def cpsd_batch_fused(channels: int, n: int, nfft: int = 0, pad: int = 0,
     channels (True) or the materialised form (gdsp_cpsd_batch_fused)."""
     return bool(lib().gdsp_cpsd_batch_fused(int(channels), int(n), int(nfft), int(pad),
                                             int(noverlap)))
-
-
-def _rows(rows):
-    """A (channels, n) float64 array of equal-length rows, or the ragged panic."""
-    if isinstance(rows, np.ndarray) and rows.ndim == 2:
-        return np.ascontiguousarray(rows, dtype=np.float64)
-    rs = [np.asarray(r, dtype=np.float64).reshape(-1) for r in rows]
-    if any(r.size != rs[0].size for r in rs):
-        raise Panic(_lib.GDSP_ERR_RAGGED, "ragged input array")
-    return np.ascontiguousarray(rs, dtype=np.float64).reshape(len(rs), rs[0].size if rs else 0)
 
 
 def CpsdBatch(x_rows, y, Fs: float, o: Optional[PwelchOptions]) -> CrossSpectra:
@@ -159,18 +155,14 @@ def CpsdBatch(x_rows, y, Fs: float, o: Optional[PwelchOptions]) -> CrossSpectra:
     if n == 0:  # pwelch.go:75-77, before the options are looked at
         e = np.zeros((channels, 0))
         return CrossSpectra(e.astype(np.complex128), e, e.copy(), e.copy(), np.zeros(0))
-    nfft, pad, noverlap, wf, scaling = resolve_options(o)
-    flen = max(pad, nfft)
-    win_seg = np.ascontiguousarray(wf(flen), dtype=np.float64)
-    win_nfft = np.ascontiguousarray(wf(nfft), dtype=np.float64)
-    lp = pad // 2 + 1
+    nfft, pad, noverlap, win_seg, win_nfft, lp, scale_off = _welch_args(o)
     pxy = np.empty((channels, lp), np.complex128)
     pxx, pyy, coh = (np.empty((channels, lp), np.float64) for _ in range(3))
     freqs = np.empty(lp, np.float64)
     lpo = _lib._I64(0)
     check(lib().gdsp_cpsd_batch(_p(x), n, _p(yy), n, 1 if yy.ndim == 1 else channels, channels, n,
                                 float(Fs), nfft, pad, noverlap, _p(win_seg), _p(win_nfft),
-                                int(not scaling), _p(pxy), _p(pxx), _p(pyy), _p(coh), _p(freqs),
+                                scale_off, _p(pxy), _p(pxx), _p(pyy), _p(coh), _p(freqs),
                                 lpo), "CpsdBatch")
     return CrossSpectra(pxy, pxx, pyy, coh, freqs)
 
@@ -224,17 +216,13 @@ def PwelchMulti(x, Fs: float, o: Optional[PwelchOptions], devices=None):
     x = np.ascontiguousarray(np.asarray(x, dtype=np.float64).reshape(-1))
     if x.size == 0:
         return np.zeros(0), np.zeros(0)
-    nfft, pad, noverlap, wf, scaling = resolve_options(o)
-    flen = max(pad, nfft)
-    win_seg = np.ascontiguousarray(wf(flen), dtype=np.float64)
-    win_nfft = np.ascontiguousarray(wf(nfft), dtype=np.float64)
-    lp = pad // 2 + 1
+    nfft, pad, noverlap, win_seg, win_nfft, lp, scale_off = _welch_args(o)
     pxx = np.empty(lp, np.float64)
     freqs = np.empty(lp, np.float64)
     lpo = _lib._I64(0)
     arr, n = _dev_array(devices)
     check(lib().gdsp_pwelch_multi(_p(x), x.size, float(Fs), nfft, pad, noverlap, _p(win_seg),
-                                  _p(win_nfft), int(not scaling), _p(pxx), _p(freqs), lpo,
+                                  _p(win_nfft), scale_off, _p(pxx), _p(freqs), lpo,
                                   arr, n), "PwelchMulti")
     return pxx[:lpo.value], freqs[:lpo.value]
 
