@@ -182,7 +182,7 @@ int gdsp_pwelch_accumulate_device(const double *d_x, int64_t n, int64_t nfft, in
     return fail(GDSP_ERR_INVALID, "bad Pwelch geometry");
   if (seg_end == seg_begin) return GDSP_OK;
   const int64_t stride = nfft - noverlap;
-  if ((seg_end - 1) * stride + nfft > n && seg_end > 1)
+  if ((seg_end - 1) * stride + nfft > n)
     return fail(GDSP_ERR_INVALID, "segments exceed the signal");
   const int64_t flen = pad > nfft ? pad : nfft;
   hipStream_t s = (hipStream_t)stream;  // NULL = the null stream
@@ -359,7 +359,7 @@ int gdsp_pwelch_batch_accumulate_device(const double *d_x, int64_t channels, int
   if (channels == 0 || seg_end == seg_begin) return GDSP_OK;
   if (!d_x || !d_win_seg || !d_acc) return fail(GDSP_ERR_INVALID, "NULL pointer");
   const int64_t stride = nfft - noverlap;
-  if ((seg_end - 1) * stride + nfft > n && seg_end > 1)
+  if ((seg_end - 1) * stride + nfft > n)
     return fail(GDSP_ERR_INVALID, "segments exceed the signal");
   const int64_t flen = pad > nfft ? pad : nfft;
   hipStream_t s = (hipStream_t)stream;

@@ -500,7 +500,12 @@ int gdsp_fft_axis_device(const void *d_in, void *d_out, const int64_t *dims, int
  * the packed segment pairs; gdsp_pwelch_finalize turns the summed
  * accumulators (over every shard / rank) into Pxx. d_win_seg: flen float64
  * window table on the device. d_acc must be zeroed by the caller before the
- * first call. */
+ * first call. Every segment of the range must lie inside the n samples:
+ * (seg_end - 1) * (nfft - noverlap) + nfft > n → GDSP_ERR_INVALID for any
+ * non-empty range, [0, 1) of a signal shorter than nfft included (the kernels
+ * read whole segments: pad such a signal to nfft first, as gdsp_pwelch does);
+ * nothing is read or written then. An empty range is GDSP_OK and touches
+ * nothing. */
 int gdsp_pwelch_accumulate_device(const double *d_x, int64_t n, int64_t nfft, int64_t pad,
                                   int64_t noverlap, int64_t seg_begin, int64_t seg_end,
                                   const double *d_win_seg, double *d_acc, void *stream);

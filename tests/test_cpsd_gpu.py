@@ -296,6 +296,48 @@ def test_accumulation_adds_without_folding(gdsp, D, f, nsegs, k):
         assert err < EXACT, name
 
 
+@pytest.mark.parametrize("k", [3, 4], ids=["odd", "even"])
+@pytest.mark.parametrize("nfft,nov,no_fused", [(100, 30, False), (4096, 2048, False),
+                                               (256, 128, True)],
+                         ids=["100", "4096", "256-NO_FUSED_CPSD"])
+def test_accumulation_adds_materialised(gdsp, D, nfft, nov, no_fused, k):
+    """The same on the materialised form (gather, the plan's transform, partial
+    sums), whose gather takes its own first segment: ranges [0, k) and [k, 7)
+    against the whole, a tail shorter than a stride behind the last segment."""
+    import torch
+    F = gdsp.fft
+    channels, nsegs = 3, 7
+    hb = nfft // 2 + 1
+    stride = nfft - nov
+    n = (nsegs - 1) * stride + nfft + min(3, stride - 1)
+    x, y = _signals(78 + nfft, channels, n, False)
+    xd, yd = _strided(x, 3), _strided(y, 5)
+    win = torch.from_numpy(np.ascontiguousarray(gdsp.window.Hann(nfft))).cuda()
+    whole = torch.zeros((channels + 1, 4, hb), dtype=torch.float64, device="cuda")
+    parts = torch.zeros((channels + 1, 4, hb), dtype=torch.float64, device="cuda")
+    whole[channels] = GUARD
+    parts[channels] = GUARD
+    prev = F.Algorithm()
+    try:
+        if no_fused:
+            F.SetAlgorithm(prev | F.ALGO_NO_FUSED_CPSD)
+        assert not gdsp.spectral.cpsd_batch_fused(channels, n, nfft, nfft, nov)
+        D.cpsd_batch_accumulate(xd, yd, nfft, nfft, nov, 0, nsegs, win, whole[:channels])
+        D.cpsd_batch_accumulate(xd, yd, nfft, nfft, nov, 0, k, win, parts[:channels])
+        D.cpsd_batch_accumulate(xd, yd, nfft, nfft, nov, k, nsegs, win, parts[:channels])
+        torch.cuda.synchronize()
+    finally:
+        F.SetAlgorithm(prev)
+    assert bool((whole[channels] == GUARD).all()) and bool((parts[channels] == GUARD).all())
+    a, b = parts[:channels].cpu().numpy(), whole[:channels].cpu().numpy()
+    assert np.isfinite(a).all() and np.isfinite(b).all()
+    for name, u, v in (("Sxx", a[:, 0], b[:, 0]), ("Syy", a[:, 1], b[:, 1]),
+                       ("Sxy", a[:, 2] + 1j * a[:, 3], b[:, 2] + 1j * b[:, 3])):
+        err = row_nrel(u, v)
+        print("adds materialised", nfft, k, name, err)
+        assert err < EXACT, name
+
+
 @pytest.mark.parametrize("nfft,nov", [(32, 16), (4096, 2048), (3000, 1000), (100, 30)])
 @pytest.mark.parametrize("one", [False, True], ids=["yc", "y1"])
 def test_other_lengths_vs_reference(gdsp, oracle, D, nfft, nov, one):
