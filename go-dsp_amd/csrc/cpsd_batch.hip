@@ -33,6 +33,11 @@
 // falls on the two signals of that segment and nothing else; no segment's
 // scale depends on another segment or on where a range begins.
 //
+// A segment of one signal whose every sample is an exact zero contributes exact
+// zeros: its X (or Y) terms, which would otherwise be the transform's roundoff
+// of the other signal, are multiplied by 0 instead of 1 (or 1 / alpha). A dead
+// channel therefore has Pyy = Pxy = 0 and a coherence of 0 / 0.
+//
 // Partials are [channel][wpc * S rows][4][hb], hb = F / 2 + 1, planes Sxx,
 // Syy, Re Sxy, Im Sxy; reduce_batch_l1 / l2 (pwelch_batch.hip) add each
 // channel's rows into acc + c 4 hb in their fixed order with F := 4 hb.
@@ -46,6 +51,16 @@
 namespace gdsp {
 
 constexpr int kCpbWaves = 4;  // waves per workgroup
+
+// The balance's range in binary orders: alpha = 2^de and 1 / alpha must be
+// normal doubles, nothing else. Every product the balance forms (alpha w y
+// at x's level going in, the Y terms times 1 / alpha at y's level coming out)
+// has the size of one of the two signals' own spectra, so it leaves the normal
+// range only where that signal's own sums do.
+constexpr int kCpsdMaxDe = 1022;
+__host__ __device__ constexpr int cpsd_clamp_de(int d) {
+  return d < -kCpsdMaxDe ? -kCpsdMaxDe : (d > kCpsdMaxDe ? kCpsdMaxDe : d);
+}
 
 template <int LOG2F>
 struct CpbGeo {
@@ -123,15 +138,16 @@ __attribute__((amdgpu_waves_per_eu(2))) void cpsd_batch_kernel(
       v[k] = {ak * wk, bk * wk};
     }
     // the segment's balance: biased exponents of max |w x| and max |w y| over
-    // the transform (0: zero or subnormal, 2047: not finite; then alpha = 1),
-    // their difference held to +-300 so that no product leaves the normal range
+    // the transform (-1: every sample an exact zero, 0: subnormal, 2047: not
+    // finite; then alpha = 1), their difference held to +-kCpsdMaxDe
     double mx = 0.0, my = 0.0;
 #pragma unroll
     for (int k = 0; k < E; ++k) {
       mx = fmax(mx, fabs(v[k].x));
       my = fmax(my, fabs(v[k].y));
     }
-    int ex = __double2hiint(mx) >> 20, ey = __double2hiint(my) >> 20;
+    int ex = mx == 0.0 ? -1 : __double2hiint(mx) >> 20;
+    int ey = my == 0.0 ? -1 : __double2hiint(my) >> 20;
 #pragma unroll
     for (int m = 1; m < (W::WAVE ? T : 64); m <<= 1) {
       ex = max(ex, __shfl_xor(ex, m));
@@ -150,9 +166,11 @@ __attribute__((amdgpu_waves_per_eu(2))) void cpsd_batch_kernel(
       ey = max(xe[1], xe[3]);
     }
     const bool bal = ex > 0 && ey > 0 && ex < 2047 && ey < 2047;
-    const int de = !bal ? 0 : (ex - ey < -300 ? -300 : (ex - ey > 300 ? 300 : ex - ey));
+    const int de = !bal ? 0 : cpsd_clamp_de(ex - ey);
     const double al = __hiloint2double((1023 + de) << 20, 0);
-    const double ia = __hiloint2double((1023 - de) << 20, 0);
+    // an all-zero segment: exact zeros for its terms, not the other signal's roundoff
+    const double ia = ey < 0 ? 0.0 : __hiloint2double((1023 - de) << 20, 0);
+    const double ox = ex < 0 ? 0.0 : 1.0;
 #pragma unroll
     for (int k = 0; k < E; ++k) v[k].y *= al;
     fft_regs<LOG2F, true, 2, 4, 0, 0, const cd *, 1, 0, NoEpi, 0, 16, W::WAVE>(v, tt, twl, lre,
@@ -178,7 +196,7 @@ __attribute__((amdgpu_waves_per_eu(2))) void cpsd_batch_kernel(
         m.x = tt == 0 ? m.x : rx;  // per component: a select of the struct goes through scratch
         m.y = tt == 0 ? m.y : ry;
       }
-      const double p = v[k].x + m.x, q = v[k].y - m.y;  // 2 X
+      const double p = (v[k].x + m.x) * ox, q = (v[k].y - m.y) * ox;  // 2 X
       const double c = (v[k].y + m.y) * ia, d = (m.x - v[k].x) * ia;  // 2 Y
       sxx[k] = fma(q, q, fma(p, p, sxx[k]));
       syy[k] = fma(d, d, fma(c, c, syy[k]));
@@ -250,7 +268,9 @@ __attribute__((amdgpu_waves_per_eu(2))) void cpsd_batch_kernel(
 // The balance of row r = c * ns + j (a block per row): alpha[r] = 2^(e_x - e_y),
 // e the binary exponents of max |w x| and max |w y| over segment seg0 + j of
 // channel c; 1 where either maximum is zero, subnormal or not finite. The
-// difference is held to +-300 so that no product leaves the normal range.
+// difference is held to +-kCpsdMaxDe.
+// A segment of all zeros is marked for cpsd_partials_kernel: alpha = 0 where
+// y's is (its Y terms are exact zeros), -alpha where only x's is (its X terms).
 __global__ __launch_bounds__(256) void cpsd_balance_kernel(
     const double *__restrict__ x, int64_t ldx, const double *__restrict__ y, int64_t ldy,
     int64_t ns, int64_t nfft, int64_t stride, int64_t seg0, const double *__restrict__ win,
@@ -277,12 +297,13 @@ __global__ __launch_bounds__(256) void cpsd_balance_kernel(
   if (t == 0) {
     const int ex = __double2hiint(mx[0]) >> 20, ey = __double2hiint(my[0]) >> 20;
     const bool bal = ex > 0 && ey > 0 && ex < 2047 && ey < 2047;
-    const int de = !bal ? 0 : (ex - ey < -300 ? -300 : (ex - ey > 300 ? 300 : ex - ey));
-    alpha[r] = __hiloint2double((1023 + de) << 20, 0);
+    const int de = !bal ? 0 : cpsd_clamp_de(ex - ey);
+    const double al = __hiloint2double((1023 + de) << 20, 0);
+    alpha[r] = my[0] == 0.0 ? 0.0 : (mx[0] == 0.0 ? -al : al);
   }
 }
 
-// Row r = c * ns + j of buf: w x + i alpha[r] w y of segment seg0 + j of
+// Row r = c * ns + j of buf: w x + i |alpha[r]| w y of segment seg0 + j of
 // channel c, zero past nfft.
 __global__ __launch_bounds__(256) void cpsd_gather_kernel(
     const double *__restrict__ x, int64_t ldx, const double *__restrict__ y, int64_t ldy,
@@ -295,7 +316,7 @@ __global__ __launch_bounds__(256) void cpsd_gather_kernel(
   cd v = {0.0, 0.0};
   if (i < nfft) {
     const int64_t o = (seg0 + j) * stride + i;
-    v = {x[c * ldx + o] * win[i], y[c * ldy + o] * win[i] * alpha[r]};
+    v = {x[c * ldx + o] * win[i], y[c * ldy + o] * win[i] * fabs(alpha[r])};
   }
   buf[tid] = v;
 }
@@ -319,8 +340,10 @@ __global__ __launch_bounds__(256) void cpsd_partials_kernel(const cd *__restrict
   for (int64_t r = r0; r < r1; ++r) {
     const cd *row = buf + (c * ns + r) * flen;
     const cd z = row[k], m = row[km];
-    const double ia = 1.0 / alpha[c * ns + r];  // exact: a power of 2
-    const double p = z.x + m.x, e = z.y - m.y;  // 2 X
+    const double al = alpha[c * ns + r];
+    const double ia = al == 0.0 ? 0.0 : 1.0 / fabs(al);  // exact: a power of 2
+    const double ox = al < 0.0 ? 0.0 : 1.0;
+    const double p = (z.x + m.x) * ox, e = (z.y - m.y) * ox;  // 2 X
     const double g = (z.y + m.y) * ia, d = (m.x - z.x) * ia;  // 2 Y
     sxx += p * p + e * e;
     syy += g * g + d * d;

@@ -119,6 +119,34 @@ enum {
 int gdsp_set_algorithm(unsigned flags);
 unsigned gdsp_get_algorithm(void);
 
+/* ---- values: scale, non-finite samples, earlier calls ----------------------
+ * What every entry below, host-pointer or device-pointer, promises about the
+ * values it is given (tests/test_values_gpu.py):
+ *  - No call depends on an earlier one: workspace, work buffers, accumulators
+ *    the library zeroes and outputs may hold anything, NaN included, when a
+ *    call starts; the same inputs give the same bits.
+ *  - No absolute threshold: inputs times 2^k give outputs times the matching
+ *    power of 2 bit for bit (transforms 2^k; Convolve and FIR 2^(a+b) for x
+ *    times 2^a and y or h times 2^b; Pwelch 2^2k; cross spectra Pxx 2^2a, Pyy
+ *    2^2b, Pxy 2^(a+b), the coherence unchanged), while no intermediate leaves
+ *    the normal range and, for cross spectra, the two levels stay within the
+ *    balance's range (gdsp_cpsd_batch). All-zero inputs give exact zeros.
+ *  - A NaN or an infinity in the input makes non-finite exactly what depends
+ *    on it, and nothing else changes by a bit:
+ *      transforms, Convolve   every element of that row (a complex NaN: NaN
+ *                             in both parts); a y shared by all rows: all rows
+ *      FFT2, FFTN             every output; one axis: the lines through it
+ *      Pwelch, batched        every bin of that channel
+ *      cross spectra          all four results of that channel, the other
+ *                             signal's P included: one transform carries a
+ *                             segment of both signals (a shared y: all channels)
+ *      FIR                    outputs [j, j + m) of that row for a bad x[j],
+ *                             and possibly more of (j - 2F, j + 2F), F =
+ *                             gdsp_fir_block's: a transform carries two blocks
+ *                             of F - m + 1 outputs and a sample is read by at
+ *                             most two transforms. scipy.signal.lfilter would
+ *                             confine it to [j, j + m). */
+
 /* ---- fft package: host pointers, synchronous ----------------------------- */
 
 /* fft.FFT — fft/fft.go:72-87. n <= 1 copies; power of 2 → Stockham radix-16
@@ -288,7 +316,15 @@ int gdsp_pwelch_batch_fused(int64_t channels, int64_t n, int64_t nfft, int64_t p
  * segment by segment, and depends on nothing but that segment. What is left is
  * a difference in level within one segment's spectra: a bin where one signal is
  * far below the other signal's largest bin carries roundoff relative to the
- * latter.
+ * latter. a spans 2^-1022 ... 2^1022, every difference in level that two
+ * normal doubles can have, so the balance itself gives up neither signal: the
+ * products it forms have the size of one of the two signals' own spectra, and
+ * a result leaves the normal range only where that signal's own sums do.
+ * a = 1 where a segment's maximum is zero, subnormal or not finite (a
+ * subnormal signal beside a normal one: its P, Pxy and the coherence are the
+ * other's roundoff, not meaningful). A segment of one signal that is
+ * all zeros contributes exact zeros to that signal's S and to Sxy (a dead
+ * channel: P = Pxy = 0, the coherence 0 / 0), not the other signal's roundoff.
  * pxy: channels × lp complex128; pxx, pyy, coh: channels × lp float64, each
  * may be NULL (skipped); freqs: lp float64.
  * Before any device call: a NULL lp_out, x, y, pxy or freqs that is needed,
