@@ -109,6 +109,7 @@ SIGNATURES = {
     "gdsp_get_algorithm": (ctypes.c_uint, []),
     "gdsp_multi_stats": (_I, [ctypes.POINTER(_I64), ctypes.POINTER(_I64), ctypes.POINTER(_I64),
                               ctypes.POINTER(_I64)]),
+    "gdsp_loop_stats": (_I, [ctypes.POINTER(_I64), ctypes.POINTER(_I64)]),
     "gdsp_fft_batch_multi": (_I, [_P, _P, _I64, _I64, _I, ctypes.POINTER(_I), _I]),
     "gdsp_pwelch_multi": (_I, [_P, _I64, _D, _I64, _I64, _I64, _P, _P, _I, _P, _P,
                                ctypes.POINTER(_I64), ctypes.POINTER(_I), _I]),

@@ -74,6 +74,13 @@ int run_queued(hipStream_t s, F &&queue) {
   return st;
 }
 
+// Counters of gdsp_loop_stats. A host chunk loop calls later_chunk(i0) in
+// every iteration: the second and later ones (i0 > 0) count. multi_unit(u)
+// stands before a launch of a Pwelch, batched-Pwelch or Cpsd kernel whose
+// workers take u pairs or groups each: u >= 2 counts.
+void later_chunk(int64_t i0);
+void multi_unit(int64_t units);
+
 // Host-pointer batched transform on the calling thread's current device.
 int host_batch(const void *x, size_t in_elem_bytes, double *out, int64_t n, int64_t batch,
                bool inv, int load);

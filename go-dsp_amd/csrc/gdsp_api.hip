@@ -33,7 +33,17 @@ using namespace gdsp_api;
 namespace {
 thread_local std::string g_last_error;
 int g_worker_pool_size = 0;  // fft.SetWorkerPoolSize mirror (no GPU meaning)
+// loop counters for tests and diagnostics (gdsp_loop_stats)
+std::atomic<int64_t> g_later_chunks{0}, g_multi_unit_launches{0};
 }  // namespace
+
+void gdsp_api::later_chunk(int64_t i0) {
+  if (i0 > 0) g_later_chunks.fetch_add(1, std::memory_order_relaxed);
+}
+
+void gdsp_api::multi_unit(int64_t units) {
+  if (units >= 2) g_multi_unit_launches.fetch_add(1, std::memory_order_relaxed);
+}
 
 int gdsp_api::fail(int st, const std::string &msg) {
   g_last_error = msg;
@@ -356,6 +366,7 @@ int exec_fourstep2(const gdsp_plan *p, const void *in, cd *out, int64_t batch, b
     src = w;
   }
   for (int64_t b0 = 0; b0 < batch; b0 += 65535) {
+    later_chunk(b0);
     const int64_t nb = batch - b0 < 65535 ? batch - b0 : 65535;
     HIPCHK(gdsp::launch_colfft(lr, inv, 2, false, src + b0 * N, w + b0 * N, C, 1, 0, 1, 0, 1,
                                pr->tw, p->tw, ln, 1.0, nb, N, s));
@@ -395,12 +406,14 @@ int exec_fourstep(const gdsp_plan *p, const void *in, cd *out, int64_t batch, bo
     src = w;
   }
   for (int64_t b0 = 0; b0 < batch; b0 += 65535) {
+    later_chunk(b0);
     const int64_t nb = batch - b0 < 65535 ? batch - b0 : 65535;
     HIPCHK(gdsp::launch_colfft(lr, inv, 2, false, src + b0 * N, w + b0 * N, C, 1, 0, 1, 0, 1,
                                pr->tw, p->tw, ln, 1.0, nb, N, s));
   }
   STCHK(exec_plan_depth(pcol, w, w, batch * R, false, gdsp::LOAD_COMPLEX, s, depth + 1));
   for (int64_t b0 = 0; b0 < batch; b0 += 65535) {
+    later_chunk(b0);
     const int64_t nb = batch - b0 < 65535 ? batch - b0 : 65535;
     HIPCHK(gdsp::launch_transpose(w + b0 * N, out + b0 * N, R, C, s, nb, inv,
                                   1.0 / (double)N));
@@ -424,6 +437,7 @@ int mixed4_col_rows(const gdsp_plan *p, const cd *src, cd *w, int64_t batch, boo
   const int64_t N = p->n, N1 = p->n1, N2 = p->n2;
   const int lr = p->pow2col ? ilog2(N1) : 0;
   for (int64_t b0 = 0; b0 < batch; b0 += 65535) {
+    later_chunk(b0);
     const int64_t nb = batch - b0 < 65535 ? batch - b0 : 65535;
     if (p->mixcol)
       HIPCHK(gdsp::jit_launch_col(p->mixcol, inv, src + b0 * N, w + b0 * N, N2, N, nb, p->p1->tw,
@@ -453,6 +467,7 @@ int exec_mixed4(const gdsp_plan *p, const void *in, cd *out, int64_t batch, bool
       src = w;
     }
     for (int64_t b0 = 0; b0 < batch; b0 += 65535) {
+      later_chunk(b0);
       const int64_t nb = batch - b0 < 65535 ? batch - b0 : 65535;
       if (p->mixcol)
         HIPCHK(gdsp::jit_launch_col(p->mixcol, inv, src + b0 * N, w + b0 * N, N2, N, nb, p->p1->tw,
@@ -485,6 +500,7 @@ int exec_mixed4(const gdsp_plan *p, const void *in, cd *out, int64_t batch, bool
     }
     STCHK(mixed4_col_rows(p, src, w, batch, inv, s));
     for (int64_t b0 = 0; b0 < batch; b0 += 65535) {
+      later_chunk(b0);
       const int64_t nb = batch - b0 < 65535 ? batch - b0 : 65535;
       HIPCHK(gdsp::launch_transpose(w + b0 * N, out + b0 * N, N1, N2, s, nb, inv,
                                     1.0 / (double)N));
@@ -502,17 +518,20 @@ int exec_mixed4(const gdsp_plan *p, const void *in, cd *out, int64_t batch, bool
     src = w2;
   }
   for (int64_t b0 = 0; b0 < batch; b0 += 65535) {
+    later_chunk(b0);
     const int64_t nb = batch - b0 < 65535 ? batch - b0 : 65535;
     HIPCHK(gdsp::launch_transpose(src + b0 * N, w1 + b0 * N, N1, N2, s, nb));
   }
   STCHK(exec_plan(p->p1, w1, w1, batch * N2, inv, gdsp::LOAD_COMPLEX, s));
   for (int64_t b0 = 0; b0 < batch; b0 += 65535) {
+    later_chunk(b0);
     const int64_t nb = batch - b0 < 65535 ? batch - b0 : 65535;
     HIPCHK(gdsp::launch_transpose(w1 + b0 * N, w2 + b0 * N, N2, N1, s, nb, false, 1.0, p->tw, N,
                                   inv));
   }
   STCHK(exec_plan(p->p2, w2, w2, batch * N1, inv, gdsp::LOAD_COMPLEX, s));
   for (int64_t b0 = 0; b0 < batch; b0 += 65535) {
+    later_chunk(b0);
     const int64_t nb = batch - b0 < 65535 ? batch - b0 : 65535;
     HIPCHK(gdsp::launch_transpose(w2 + b0 * N, out + b0 * N, N1, N2, s, nb));
   }
@@ -552,6 +571,7 @@ int exec_bluestein_composed(const gdsp_plan *p, const cd *in, cd *out, int64_t b
     for (int pass = 1; pass <= 2; ++pass) {
       STCHK(mixed4_col_rows(mp, da, w, batch, false, s));
       for (int64_t b0 = 0; b0 < batch; b0 += 65535) {
+        later_chunk(b0);
         const int64_t nb = batch - b0 < 65535 ? batch - b0 : 65535;
         if (pass == 1)
           HIPCHK(gdsp::launch_transpose_blu(w + b0 * M, da + b0 * M, mp->n1, mp->n2, nb, 1, p->n,
@@ -579,6 +599,7 @@ int exec_bluestein_composed(const gdsp_plan *p, const cd *in, cd *out, int64_t b
     cd *w = (cd *)work.p;
     for (int pass = 1; pass <= 2; ++pass) {
       for (int64_t b0 = 0; b0 < batch; b0 += 65535) {
+        later_chunk(b0);
         const int64_t nb = batch - b0 < 65535 ? batch - b0 : 65535;
         if (pass == 1)
           HIPCHK(gdsp::launch_colfft_chirp(lr2, inv, in + b0 * p->n, w + b0 * M, C, p->n, p->chirp,
@@ -611,12 +632,14 @@ int exec_bluestein_composed(const gdsp_plan *p, const cd *in, cd *out, int64_t b
     cd *w = (cd *)work.p;
     for (int pass = 1; pass <= 2; ++pass) {
       for (int64_t b0 = 0; b0 < batch; b0 += 65535) {
+        later_chunk(b0);
         const int64_t nb = batch - b0 < 65535 ? batch - b0 : 65535;
         HIPCHK(gdsp::launch_colfft(lr, false, 2, false, da + b0 * M, w + b0 * M, C, 1, 0, 1, 0, 1,
                                    pr->tw, p->mplan->tw, p->log2m, 1.0, nb, M, s));
       }
       STCHK(exec_plan_depth(pcol, w, w, batch * R, false, gdsp::LOAD_COMPLEX, s, 1));
       for (int64_t b0 = 0; b0 < batch; b0 += 65535) {
+        later_chunk(b0);
         const int64_t nb = batch - b0 < 65535 ? batch - b0 : 65535;
         if (pass == 1)
           HIPCHK(gdsp::launch_transpose_blu(w + b0 * M, da + b0 * M, R, C, nb, 1, p->n, p->bhat,
@@ -834,6 +857,13 @@ int gdsp_set_algorithm(unsigned flags) {
 }
 
 unsigned gdsp_get_algorithm(void) { return g_algo.load(); }
+
+int gdsp_loop_stats(int64_t *later_chunks, int64_t *multi_unit_launches) {
+  if (later_chunks) *later_chunks = g_later_chunks.load(std::memory_order_relaxed);
+  if (multi_unit_launches)
+    *multi_unit_launches = g_multi_unit_launches.load(std::memory_order_relaxed);
+  return GDSP_OK;
+}
 
 int gdsp_fft(const double *x, double *out, int64_t n) {
   return host_batch(x, sizeof(cd), out, n, 1, false, gdsp::LOAD_COMPLEX);
@@ -1090,6 +1120,7 @@ static int fir_rows(const double *d_x, int64_t ldx, const double *d_h, int64_t h
   cd *buf = work + h_rows * F;
   const int64_t rows = fir_chunk_rows(F, total);
   for (int64_t g0 = 0; g0 < total; g0 += rows) {
+    later_chunk(g0);
     const int64_t cnt = total - g0 < rows ? total - g0 : rows;
     HIPCHK(gdsp::launch_fir_gather(d_x, ldx, g0, cnt, tpr, n, m, F, buf, s));
     STCHK(exec_plan(p, buf, buf, cnt, false, gdsp::LOAD_COMPLEX, s));
@@ -1251,6 +1282,7 @@ static int fft_axis(const cd *src, cd *cur, cd *other, int64_t L, int64_t inner,
     if (l2) STCHK(get_plan((int64_t)1 << l2, &p2));
     const int64_t R1 = (int64_t)1 << l1, R2 = (int64_t)1 << l2;
     for (int64_t o0 = 0; o0 < outer; o0 += 65535) {
+      later_chunk(o0);
       const int64_t nb = outer - o0 < 65535 ? outer - o0 : 65535;
       const cd *s0 = src + o0 * L * inner;
       cd *c0 = cur + o0 * L * inner, *t0 = other + o0 * L * inner;
@@ -1269,11 +1301,13 @@ static int fft_axis(const cd *src, cd *cur, cd *other, int64_t L, int64_t inner,
     return GDSP_OK;
   }
   for (int64_t o0 = 0; o0 < outer; o0 += 65535) {
+    later_chunk(o0);
     const int64_t nb = outer - o0 < 65535 ? outer - o0 : 65535;
     HIPCHK(gdsp::launch_transpose(src + o0 * L * inner, other + o0 * L * inner, L, inner, s, nb));
   }
   STCHK(exec_plan(pl, other, other, outer * inner, inv, gdsp::LOAD_COMPLEX, s));
   for (int64_t o0 = 0; o0 < outer; o0 += 65535) {
+    later_chunk(o0);
     const int64_t nb = outer - o0 < 65535 ? outer - o0 : 65535;
     HIPCHK(gdsp::launch_transpose(other + o0 * L * inner, cur + o0 * L * inner, inner, L, s, nb));
   }

@@ -198,6 +198,7 @@ int gdsp_pwelch_accumulate_device(const double *d_x, int64_t n, int64_t nfft, in
     const bool half = 2 * noverlap == nfft && flen == nfft;
     int64_t gpw = 0, nblk = 0, nrows = 0;
     gdsp::pwelch_wave_geometry(p->log2n, half, nseg, &gpw, &nblk, &nrows);
+    multi_unit(gpw);
     STCHK(pt.alloc(nrows, flen, s));
     HIPCHK(gdsp::launch_pwelch_wave(p->log2n, half, d_x, nfft, stride, seg_begin, seg_end, gpw,
                                     nblk, d_win_seg, p->tw, pt.p(), s));
@@ -212,6 +213,7 @@ int gdsp_pwelch_accumulate_device(const double *d_x, int64_t n, int64_t nfft, in
   int64_t ppw = 0, nworkers = 0;
   auto workers = [&](int64_t target) -> int {
     pair_workers(npairs, target, &ppw, &nworkers);
+    multi_unit(ppw);
     return pt.alloc(nworkers, flen, s);
   };
   if (fused && p->kind == KIND_LDS && p->log2n >= 4) {
@@ -269,6 +271,7 @@ int gdsp_pwelch_accumulate_device(const double *d_x, int64_t n, int64_t nfft, in
   STCHK(buf.alloc((size_t)rows * (size_t)flen * sizeof(cd), s, SLOT_PW_BUF));
   STCHK(pt.alloc((rows + kRpp - 1) / kRpp, flen, s));
   for (int64_t r0 = 0; r0 < npairs; r0 += rows) {
+    later_chunk(r0);
     const int64_t nr = (npairs - r0) < rows ? (npairs - r0) : rows;
     HIPCHK(gdsp::launch_segments_to_complex(d_x, nfft, flen, stride, seg_begin + 2 * r0, seg_end,
                                             nr, d_win_seg, (cd *)buf.p, s));
@@ -366,9 +369,11 @@ int gdsp_pwelch_batch_accumulate_device(const double *d_x, int64_t channels, int
   gdsp_plan *p = nullptr;
   if (pwelch_batch_fused(flen, stride)) STCHK(get_plan(flen, &p));
   if (!p || p->kind != KIND_LDS) {
-    for (int64_t c = 0; c < channels; ++c)
+    for (int64_t c = 0; c < channels; ++c) {
+      later_chunk(c);
       STCHK(gdsp_pwelch_accumulate_device(d_x + c * ldx, n, nfft, pad, noverlap, seg_begin,
                                           seg_end, d_win_seg, d_acc + c * flen, stream));
+    }
     return GDSP_OK;
   }
   const bool half = 2 * noverlap == nfft && flen == nfft;
@@ -379,6 +384,8 @@ int gdsp_pwelch_batch_accumulate_device(const double *d_x, int64_t channels, int
   STCHK(pt.alloc_batch(cpl, rows, flen, s));
   for (int64_t c0 = 0; c0 < channels; c0 += cpl) {
     const int64_t nc = channels - c0 < cpl ? channels - c0 : cpl;
+    later_chunk(c0);
+    multi_unit(gpw);
     HIPCHK(gdsp::launch_pwelch_batch(p->log2n, half, d_x + c0 * ldx, ldx, nc, wpc, nfft, stride,
                                      seg_begin, seg_end, gpw, d_win_seg, p->tw, pt.p(), s));
     STCHK(pt.reduce_batch(nc, rows, flen, d_acc + c0 * flen, s));
@@ -495,6 +502,8 @@ int gdsp_cpsd_batch_accumulate_device(const double *d_x, int64_t ldx, const doub
     STCHK(pt.alloc_batch(cpl, rows, 4 * hb, s));
     for (int64_t c0 = 0; c0 < channels; c0 += cpl) {
       const int64_t nc = channels - c0 < cpl ? channels - c0 : cpl;
+      later_chunk(c0);
+      multi_unit(gpw);
       HIPCHK(gdsp::launch_cpsd_batch(p->log2n, d_x + c0 * ldx, ldx, d_y + c0 * ldyk, ldyk, nc, wpc,
                                      nfft, stride, seg_begin, seg_end, gpw, d_win_seg, p->tw,
                                      pt.p(), s));
@@ -518,8 +527,10 @@ int gdsp_cpsd_batch_accumulate_device(const double *d_x, int64_t ldx, const doub
   STCHK(pt.alloc_batch(cpl, (ns_max + kRpp - 1) / kRpp, 4 * hb, s));
   for (int64_t c0 = 0; c0 < channels; c0 += cpl) {
     const int64_t nc = channels - c0 < cpl ? channels - c0 : cpl;
+    later_chunk(c0);
     for (int64_t j0 = 0; j0 < nseg; j0 += ns_max) {
       const int64_t ns = nseg - j0 < ns_max ? nseg - j0 : ns_max;
+      later_chunk(j0);
       HIPCHK(gdsp::launch_cpsd_balance(d_x + c0 * ldx, ldx, d_y + c0 * ldyk, ldyk, nc, ns, nfft,
                                        stride, seg_begin + j0, d_win_seg, alpha, s));
       HIPCHK(gdsp::launch_cpsd_gather(d_x + c0 * ldx, ldx, d_y + c0 * ldyk, ldyk, nc, ns, nfft,

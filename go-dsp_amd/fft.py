@@ -321,6 +321,16 @@ def MultiStats() -> dict:
                     (a.value for a in v)))
 
 
+def LoopStats() -> dict:
+    """gdsp_loop_stats: second-or-later iterations of the host chunk loops, and
+    Pwelch / Cpsd launches whose workers took two or more pairs or groups,
+    since process start."""
+    import ctypes
+    v = [ctypes.c_int64() for _ in range(2)]
+    check(lib().gdsp_loop_stats(*[ctypes.byref(a) for a in v]), "LoopStats")
+    return dict(zip(("later_chunks", "multi_unit_launches"), (a.value for a in v)))
+
+
 def FFTBatchMulti(x, inverse: bool = False, devices=None) -> np.ndarray:
     """FFTBatch split over `devices` (None: the device set): contiguous row
     shards, one per device, no collective (gdsp_fft_batch_multi)."""

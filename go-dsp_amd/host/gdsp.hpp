@@ -319,6 +319,16 @@ inline MultiStats GetMultiStats() {
   return m;
 }
 
+// How calls were cut into pieces (gdsp_loop_stats).
+struct LoopStats {
+  int64_t later_chunks = 0, multi_unit_launches = 0;
+};
+inline LoopStats GetLoopStats() {
+  LoopStats l;
+  check(gdsp_loop_stats(&l.later_chunks, &l.multi_unit_launches), "LoopStats");
+  return l;
+}
+
 // Algorithm selection (gdsp_fft.h GDSP_ALGO_*; no reference equivalent).
 inline void SetAlgorithm(unsigned flags) { check(gdsp_set_algorithm(flags), "SetAlgorithm"); }
 inline unsigned Algorithm() { return gdsp_get_algorithm(); }

@@ -398,6 +398,19 @@ int gdsp_get_devices(int *devices, int cap);
  * NULL. */
 int gdsp_multi_stats(int64_t *batch_calls, int64_t *pwelch_calls, int64_t *rccl_reduces,
                      int64_t *host_reduces);
+/* How calls were cut into pieces since process start (diagnostics and tests;
+ * host-side counters, no kernel takes part). later_chunks: second and later
+ * iterations of the host loops that cut one call into several launches (the
+ * materialised Pwelch's pair chunks and Cpsd's channel and segment runs, the
+ * channels-per-launch loops of the fused batched Pwelch and Cpsd, the channel
+ * loop of the batched Pwelch where it has no fused kernel, the composed FIR's
+ * transform chunks, and the 65535-row pieces of gdsp_fft_axis_device /
+ * gdsp_fftn_device and of the multi-pass, four-step and chirp-z executors).
+ * multi_unit_launches: launches of a Pwelch, batched-Pwelch or Cpsd kernel
+ * whose persistent workers each take at least two pairs (or pair groups). A
+ * test reads both before and after a call to prove that the call reached the
+ * path it was shaped for. Any pointer may be NULL. */
+int gdsp_loop_stats(int64_t *later_chunks, int64_t *multi_unit_launches);
 
 /* fft.FFT / fft.IFFT over `batch` rows of n complex128 (as gdsp_fft_batch),
  * always split over `devices` (NULL or ndev = 0: the library's device set);
