@@ -85,6 +85,15 @@ SIGNATURES = {
                                                _I64, _I64, _I64, _P, _P, _P]),
     "gdsp_cpsd_batch_finalize_device": (_I, [_P, _I64, _I64, _I64, _I64, _I64, _P, _D, _I, _P,
                                              _P, _P, _P, _P, _P]),
+    "gdsp_stft_batch": (_I, [_P, _I64, _I64, _I64, _I64, _I64, _I64, _P, _P, ctypes.POINTER(_I64),
+                             ctypes.POINTER(_I64)]),
+    "gdsp_spectrogram_batch": (_I, [_P, _I64, _I64, _I64, _D, _I64, _I64, _I64, _P, _P, _I, _P, _P,
+                                    _P, ctypes.POINTER(_I64), ctypes.POINTER(_I64)]),
+    "gdsp_stft_batch_fused": (_I, [_I64, _I64, _I64, _I64, _I64]),
+    "gdsp_stft_batch_device": (_I, [_P, _I64, _I64, _I64, _I64, _I64, _I64, _I64, _I64, _P, _P,
+                                    _I64, _I64, _P]),
+    "gdsp_spectrogram_batch_device": (_I, [_P, _I64, _I64, _I64, _I64, _I64, _I64, _I64, _I64, _P,
+                                           _D, _P, _I64, _I64, _P]),
     "gdsp_wav_read_floats_planar_device": (_I, [_P, _I64, _I64, _I, _I, _P, _I64, _P]),
     "gdsp_window_hann": (_I, [_I64, _P]),
     "gdsp_plan_create": (_I, [_I64, ctypes.POINTER(_P)]),

@@ -116,6 +116,29 @@ hipError_t launch_cpsd_partials(const cd *buf, int64_t channels, int64_t ns, int
 hipError_t launch_cpsd_finalize(const double *acc, int64_t channels, int64_t hb, int64_t lp,
                                 int64_t nsegs, double norm, cd *pxy, double *pxx, double *pyy,
                                 double *coh, hipStream_t s);
+// the per-segment spectra of a planar batch (stft_batch.hip): row (c, s -
+// seg_begin) of out, at element c ld_chan + (s - seg_begin) ld_seg, is the
+// first lp bins of the F-point transform of segment s of channel c, windowed
+// and zero-padded: complex128 (power = false), or float64 c_j |X|^2 / norm.
+// The fused kernel for the lengths of the batched Pwelch (packed segment
+// pairs, balanced by a power of 2 per pair, its geometry without partials:
+// workers per channel and pair groups per worker); the materialised form for
+// every other length: rows w x_s of segments [seg0, seg0 + ns) of every
+// channel as float64 rows of flen, then, after the plan's transform of real
+// rows, launch_stft_rows into the caller's layout at segment row `row0`.
+bool stft_batch_applies(int log2f);
+void stft_batch_geometry(int log2f, int64_t channels, int64_t nsegs, int64_t *wpc, int64_t *gpw);
+hipError_t launch_stft_batch(int log2f, bool power, const double *x, int64_t ldx, int64_t channels,
+                             int64_t wpc, int64_t nfft, int64_t stride, int64_t seg_begin,
+                             int64_t seg_end, int64_t gpw, const double *win, const cd *tw,
+                             void *out, int64_t lp, int64_t ld_seg, int64_t ld_chan, double norm,
+                             hipStream_t s);
+hipError_t launch_stft_gather(const double *x, int64_t ldx, int64_t channels, int64_t ns,
+                              int64_t nfft, int64_t flen, int64_t stride, int64_t seg0,
+                              const double *win, double *buf, hipStream_t s);
+hipError_t launch_stft_rows(const cd *buf, int64_t channels, int64_t ns, int64_t flen, int64_t lp,
+                            bool power, double norm, void *out, int64_t row0, int64_t ld_seg,
+                            int64_t ld_chan, hipStream_t s);
 // fused Pwelch on a compiled specialisation (d = the plan's specialisation
 // descriptor, d.n = max(pad, nfft)); workers per block, 0 if d is none or
 // its kernel cannot stage a pair of span = stride + nfft samples

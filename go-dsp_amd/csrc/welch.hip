@@ -1,8 +1,9 @@
 // welch.hip — the Welch family of the C ABI (include/gdsp_fft.h): Pwelch, the
-// batched Pwelch over the channels of a planar batch, and the batched cross
-// spectra (Cpsd, coherence); with them spectral.Segment's count and the Hann
-// table. Host arithmetic only: the kernels are in pwelch_*.hip, cpsd_batch.hip
-// and the transform files, behind launch.hpp.
+// batched Pwelch over the channels of a planar batch, the batched cross
+// spectra (Cpsd, coherence) and the per-segment spectra (STFT, spectrogram);
+// with them spectral.Segment's count and the Hann table. Host arithmetic only:
+// the kernels are in pwelch_*.hip, cpsd_batch.hip, stft_batch.hip and the
+// transform files, behind launch.hpp.
 #include <math.h>
 
 #include <string>
@@ -153,11 +154,153 @@ bool cpsd_batch_fused(int64_t flen, int64_t stride) {
   return batch_fused(flen, stride, gdsp::cpsd_batch_applies, GDSP_ALGO_NO_FUSED_CPSD);
 }
 
-// gdsp_pwelch_batch_fused / gdsp_cpsd_batch_fused: the predicate on a call's options
+// The fused per-segment kernel (stft_batch.hip) serves the same lengths and
+// strides; every other one, and any shape under GDSP_ALGO_NO_FUSED_STFT, runs
+// the materialised form.
+bool stft_batch_fused(int64_t flen, int64_t stride) {
+  return batch_fused(flen, stride, gdsp::stft_batch_applies, GDSP_ALGO_NO_FUSED_STFT);
+}
+
+// gdsp_pwelch_batch_fused / gdsp_cpsd_batch_fused / gdsp_stft_batch_fused: the
+// predicate on a call's options
 int fused_answer(bool (*fused)(int64_t, int64_t), int64_t channels, int64_t n, int64_t nfft,
                  int64_t pad, int64_t noverlap) {
   if (channels < 0 || n < 0 || !welch_defaults(&nfft, &pad)) return 0;
   return fused(pad > nfft ? pad : nfft, nfft - noverlap) ? 1 : 0;
+}
+
+// ---- per-segment spectra: STFT (complex rows) and spectrogram (power rows) ----
+
+// elements of a host call's device output, and complex elements of a
+// materialised chunk's rows: 512 MiB of complex128, as the other entries
+constexpr int64_t kStftChunkElems = (int64_t)1 << 25;
+
+// gdsp_stft_batch_device / gdsp_spectrogram_batch_device
+int stft_device(bool power, const double *d_x, int64_t ldx, int64_t channels, int64_t n,
+                int64_t nfft, int64_t pad, int64_t noverlap, int64_t seg_begin, int64_t seg_end,
+                const double *d_win_seg, double norm, void *d_out, int64_t ld_seg, int64_t ld_chan,
+                void *stream) {
+  if (nfft <= 0 || pad <= 0 || seg_begin < 0 || seg_end < seg_begin)
+    return fail(GDSP_ERR_INVALID, "bad STFT geometry");
+  if (channels < 0 || n < 0 || (channels > 1 && ldx < n))
+    return fail(GDSP_ERR_INVALID, "bad batch geometry");
+  const int64_t lp = pad / 2 + 1, nseg = seg_end - seg_begin;
+  if (ld_seg < lp || (channels > 1 && nseg > 0 && ld_chan / nseg < ld_seg))
+    return fail(GDSP_ERR_INVALID, "output strides below the rows");
+  const int64_t stride = nfft - noverlap;
+  // Segment divides by the stride only where there is more than one segment
+  if (stride == 0 && seg_end > 1) return fail(GDSP_ERR_DIVIDE_BY_ZERO, "integer divide by zero");
+  if (channels == 0 || nseg == 0) return GDSP_OK;
+  if (!d_x || !d_win_seg || !d_out) return fail(GDSP_ERR_INVALID, "NULL pointer");
+  // a negative stride (Noverlap > NFFT) leaves at most segment 0 (Segment)
+  if ((seg_end - 1) * stride + nfft > n || (stride < 0 && seg_end > 1))
+    return fail(GDSP_ERR_INVALID, "segments exceed the signal");
+  const int64_t flen = pad > nfft ? pad : nfft;
+  const size_t esize = power ? sizeof(double) : sizeof(cd);
+  hipStream_t s = (hipStream_t)stream;
+  gdsp_plan *p = nullptr;
+  STCHK(get_plan(flen, &p));
+  // the plan's kind is checked because the kernel reads that plan's twiddle
+  // table (gdsp_cpsd_batch_accumulate_device)
+  if (stft_batch_fused(flen, stride) && p->kind == KIND_LDS) {
+    int64_t wpc = 0, gpw = 0;
+    gdsp::stft_batch_geometry(p->log2n, channels, nseg, &wpc, &gpw);
+    multi_unit(gpw);
+    HIPCHK(gdsp::launch_stft_batch(p->log2n, power, d_x, ldx, channels, wpc, nfft, stride,
+                                   seg_begin, seg_end, gpw, d_win_seg, p->tw, d_out, lp, ld_seg,
+                                   ld_chan, norm, s));
+    return GDSP_OK;
+  }
+  // materialised form: chunks of at most 512 MiB of complex rows (and their
+  // real rows), whole channels where a channel's segments fit, else one
+  // channel's segments in runs; one real segment per transform
+  int64_t maxrows = kStftChunkElems / flen;
+  if (maxrows < 1) maxrows = 1;
+  const int64_t ns_max = nseg < maxrows ? nseg : maxrows;  // segments per run
+  int64_t cpl = maxrows / ns_max;                           // channels per launch
+  if (cpl > channels) cpl = channels;
+  DevBuf rows, buf;
+  STCHK(rows.alloc((size_t)cpl * (size_t)ns_max * (size_t)flen * sizeof(double), s, SLOT_ST_ROWS));
+  STCHK(buf.alloc((size_t)cpl * (size_t)ns_max * (size_t)flen * sizeof(cd), s, SLOT_PW_BUF));
+  for (int64_t c0 = 0; c0 < channels; c0 += cpl) {
+    const int64_t nc = channels - c0 < cpl ? channels - c0 : cpl;
+    later_chunk(c0);
+    void *const oc = (char *)d_out + (size_t)c0 * (size_t)ld_chan * esize;
+    for (int64_t j0 = 0; j0 < nseg; j0 += ns_max) {
+      const int64_t ns = nseg - j0 < ns_max ? nseg - j0 : ns_max;
+      later_chunk(j0);
+      HIPCHK(gdsp::launch_stft_gather(d_x + c0 * ldx, ldx, nc, ns, nfft, flen, stride,
+                                      seg_begin + j0, d_win_seg, (double *)rows.p, s));
+      STCHK(exec_plan(p, rows.p, (cd *)buf.p, nc * ns, false, gdsp::LOAD_REAL, s));
+      HIPCHK(gdsp::launch_stft_rows((const cd *)buf.p, nc, ns, flen, lp, power, norm, oc, j0,
+                                    ld_seg, ld_chan, s));
+    }
+  }
+  return GDSP_OK;
+}
+
+// gdsp_stft_batch / gdsp_spectrogram_batch: out is channels x nsegs x lp,
+// dense. The device output holds at most kStftChunkElems elements: segment
+// ranges that begin at even indices (the pairs of the fused kernel, and with
+// them every bit of a row, do not depend on where the cut falls), each copied
+// back before the next is computed.
+int stft_host(bool power, const double *x, int64_t channels, int64_t n, int64_t ldx, double fs,
+              int64_t nfft, int64_t pad, int64_t noverlap, const double *win_seg,
+              const double *win_nfft, int scale_off, double *out, double *freqs, double *times,
+              int64_t *nsegs_out, int64_t *lp_out) {
+  if (!nsegs_out || !lp_out) return fail(GDSP_ERR_INVALID, "NULL pointer");
+  *nsegs_out = *lp_out = 0;
+  if (channels < 0 || n < 0) return fail(GDSP_ERR_INVALID, "negative size");
+  if (n == 0) return GDSP_OK;
+  if (!welch_defaults(&nfft, &pad)) return fail(GDSP_ERR_INVALID, "negative NFFT/Pad");
+  if (channels > 1 && ldx < n) return fail(GDSP_ERR_INVALID, "ldx below the channel length");
+  WelchShape w;
+  STCHK(welch_shape(n, nfft, pad, noverlap, &w));
+  if ((power && (!freqs || (w.nsegs > 0 && !times))) ||
+      (channels > 0 && w.nsegs > 0 && (!x || !out)))
+    return fail(GDSP_ERR_INVALID, "NULL pointer");
+  const int64_t stride = nfft - noverlap;
+  if (power) {
+    welch_freqs(pad, fs, freqs);
+    // the segment's centre (scipy.signal.spectrogram, matplotlib specgram)
+    for (int64_t i = 0; i < w.nsegs; ++i)
+      times[i] = ((double)(i * stride) + 0.5 * (double)nfft) / fs;
+  }
+  *nsegs_out = w.nsegs;
+  *lp_out = w.lp;
+  if (channels == 0 || w.nsegs == 0) return GDSP_OK;
+  const double norm = power ? welch_norm(win_nfft, nfft, fs, scale_off) : 1.0;
+  std::vector<double> hseg;
+  win_seg = hann_or(win_seg, w.flen, hseg);
+  int dev = 0;
+  STCHK(current_device(&dev));
+  hipStream_t s = thread_stream(dev);
+  if (!s) return fail(GDSP_ERR_HIP, "stream creation failed");
+  const int64_t dpe = power ? 1 : 2;  // doubles per output element
+  int64_t per = (kStftChunkElems / (channels * w.lp)) & ~(int64_t)1;  // segments per range: even
+  if (per < 2) per = 2;
+  if (per > w.nsegs) per = w.nsegs;
+  DevBuf dx, dw, dout;
+  STCHK(dx.alloc((size_t)channels * (size_t)w.lx * sizeof(double), s, SLOT_IN));
+  STCHK(dw.alloc((size_t)w.flen * sizeof(double), s, SLOT_AUX));
+  STCHK(dout.alloc((size_t)channels * (size_t)per * (size_t)w.lp * (size_t)dpe * sizeof(double), s,
+                   SLOT_ST_OUT));
+  for (int64_t s0 = 0; s0 < w.nsegs; s0 += per) {
+    const int64_t ns = w.nsegs - s0 < per ? w.nsegs - s0 : per;
+    later_chunk(s0);
+    STCHK(run_queued(s, [&]() -> int {
+      if (s0 == 0) {
+        STCHK(stage_rows((double *)dx.p, x, channels, n, ldx, w.lx, s));
+        STCHK(copy_h2d(dw.p, win_seg, (size_t)w.flen * sizeof(double), s));
+      }
+      return stft_device(power, (const double *)dx.p, w.lx, channels, w.lx, nfft, pad, noverlap, s0,
+                         s0 + ns, (const double *)dw.p, norm, dout.p, w.lp, ns * w.lp, s);
+    }));
+    // channel c's rows [s0, s0 + ns): dense on the device, nsegs rows apart on the host
+    STCHK(unstage_rows(out + s0 * w.lp * dpe, (const double *)dout.p, channels, ns * w.lp * dpe,
+                       w.nsegs * w.lp * dpe, s));
+  }
+  return GDSP_OK;
 }
 
 }  // namespace
@@ -629,6 +772,44 @@ int gdsp_cpsd_batch(const double *x, int64_t ldx, const double *y, int64_t ldy, 
     if (outs[i]) STCHK(copy_d2h(outs[i], dev_out[i], cl * sizeof(double), s));
   *lp_out = lp;
   return GDSP_OK;
+}
+
+// ---- per-segment spectra: STFT and spectrogram --------------------------------
+
+int gdsp_stft_batch_fused(int64_t channels, int64_t n, int64_t nfft, int64_t pad,
+                          int64_t noverlap) {
+  return fused_answer(stft_batch_fused, channels, n, nfft, pad, noverlap);
+}
+
+int gdsp_stft_batch_device(const double *d_x, int64_t ldx, int64_t channels, int64_t n,
+                           int64_t nfft, int64_t pad, int64_t noverlap, int64_t seg_begin,
+                           int64_t seg_end, const double *d_win_seg, void *d_out, int64_t ld_seg,
+                           int64_t ld_chan, void *stream) {
+  return stft_device(false, d_x, ldx, channels, n, nfft, pad, noverlap, seg_begin, seg_end,
+                     d_win_seg, 1.0, d_out, ld_seg, ld_chan, stream);
+}
+
+int gdsp_spectrogram_batch_device(const double *d_x, int64_t ldx, int64_t channels, int64_t n,
+                                  int64_t nfft, int64_t pad, int64_t noverlap, int64_t seg_begin,
+                                  int64_t seg_end, const double *d_win_seg, double norm,
+                                  double *d_out, int64_t ld_seg, int64_t ld_chan, void *stream) {
+  return stft_device(true, d_x, ldx, channels, n, nfft, pad, noverlap, seg_begin, seg_end,
+                     d_win_seg, norm, d_out, ld_seg, ld_chan, stream);
+}
+
+int gdsp_stft_batch(const double *x, int64_t channels, int64_t n, int64_t ldx, int64_t nfft,
+                    int64_t pad, int64_t noverlap, const double *win_seg, double *out,
+                    int64_t *nsegs_out, int64_t *lp_out) {
+  return stft_host(false, x, channels, n, ldx, 1.0, nfft, pad, noverlap, win_seg, nullptr, 1, out,
+                   nullptr, nullptr, nsegs_out, lp_out);
+}
+
+int gdsp_spectrogram_batch(const double *x, int64_t channels, int64_t n, int64_t ldx, double fs,
+                           int64_t nfft, int64_t pad, int64_t noverlap, const double *win_seg,
+                           const double *win_nfft, int scale_off, double *out, double *freqs,
+                           double *times, int64_t *nsegs_out, int64_t *lp_out) {
+  return stft_host(true, x, channels, n, ldx, fs, nfft, pad, noverlap, win_seg, win_nfft,
+                   scale_off, out, freqs, times, nsegs_out, lp_out);
 }
 
 }  // extern "C"

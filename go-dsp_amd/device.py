@@ -365,6 +365,85 @@ def cpsd_batch(x, y, Fs: float, o, acc=None, stream=None, out=None):
     return spectral.CrossSpectra(outs[0], outs[1], outs[2], outs[3], freqs)
 
 
+def _segment_rows(power: bool, x, Fs: float, o, out, seg_begin: int, seg_end, stream):
+    """stft_batch / spectrogram_batch: the rows of segments [seg_begin, seg_end)
+    of every row of x into out, (channels, seg_end - seg_begin, lp)."""
+    import contextlib
+
+    import numpy as np
+
+    from . import distributed, spectral
+    torch = _torch()
+    assert x.is_cuda and x.dtype == torch.float64 and x.dim() == 2
+    channels, n = x.shape
+    dev = x.device
+    dtype = torch.float64 if power else torch.complex128
+    if n == 0:  # pwelch.go:75-77
+        return torch.zeros((channels, 0, 0), dtype=dtype, device=dev), np.zeros(0), np.zeros(0)
+    assert x.stride(1) == 1, "rows must have unit inner stride"
+    nfft, pad, noverlap, wf, scaling = spectral.resolve_options(o)
+    flen, lp = max(pad, nfft), pad // 2 + 1
+    ctx = torch.cuda.stream(stream) if stream is not None else contextlib.nullcontext()
+    with torch.cuda.device(dev), ctx:
+        if n < nfft:  # pwelch.go:97-99: zero-padded to nfft
+            x = torch.nn.functional.pad(x, (0, nfft - n))
+        n = x.shape[1]
+        ldx = x.stride(0) if channels > 1 else n
+        assert ldx >= n, "rows overlap"
+        nsegs = spectral.segment_count(n, nfft, noverlap)
+        seg_end = nsegs if seg_end is None else int(seg_end)
+        seg_begin = int(seg_begin)
+        assert 0 <= seg_begin <= seg_end <= nsegs, (seg_begin, seg_end, nsegs)
+        ns = seg_end - seg_begin
+        if out is None:
+            out = torch.empty((channels, ns, lp), dtype=dtype, device=dev)
+        assert out.is_cuda and out.dtype == dtype and out.device == dev
+        assert tuple(out.shape) == (channels, ns, lp), (tuple(out.shape), (channels, ns, lp))
+        assert lp == 1 or out.stride(2) == 1, "rows must have unit inner stride"
+        ld_seg = out.stride(1) if ns > 1 else lp
+        ld_chan = out.stride(0) if channels > 1 else ns * ld_seg
+        freqs = spectral.stft_freqs(pad, Fs)
+        times = spectral.stft_times(seg_begin, seg_end, nfft, noverlap, Fs)
+        if channels == 0 or ns == 0:
+            return out, freqs, times
+        win_seg = distributed._device_window(wf, flen, dev, torch)
+        sp = _stream_ptr(stream, dev)
+        if power:
+            # gdsp_pwelch_finalize's norm: the window's squares summed in order
+            w = np.ascontiguousarray(wf(nfft), dtype=np.float64)
+            norm = float(np.cumsum(w * w)[-1]) if w.size else 0.0
+            if scaling:
+                norm *= float(Fs)
+            check(lib().gdsp_spectrogram_batch_device(
+                _ptr(x), ldx, channels, n, nfft, pad, noverlap, seg_begin, seg_end, _ptr(win_seg),
+                norm, _ptr(out), ld_seg, ld_chan, sp), "spectrogram_batch_device")
+        else:
+            check(lib().gdsp_stft_batch_device(
+                _ptr(x), ldx, channels, n, nfft, pad, noverlap, seg_begin, seg_end, _ptr(win_seg),
+                _ptr(out), ld_seg, ld_chan, sp), "stft_batch_device")
+    return out, freqs, times
+
+
+def stft_batch(x, o, out=None, seg_begin: int = 0, seg_end=None, stream=None, Fs: float = 1.0):
+    """spectral.StftBatch on a (channels, n) float64 CUDA tensor (unit inner
+    stride, any row stride), device-resident: the complex128 rows of segments
+    [seg_begin, seg_end) (None: all) of every channel. Returns (X, freqs,
+    times) with X (channels, seg_end - seg_begin, pad // 2 + 1) on x's device
+    and numpy freqs and times (of Fs; the default 1.0 gives cycles per sample
+    and sample counts). out: any view of that shape whose last dimension is
+    contiguous; its strides are the rows' (gdsp_stft_batch_device), and nothing
+    between the rows is written."""
+    return _segment_rows(False, x, Fs, o, out, seg_begin, seg_end, stream)
+
+
+def spectrogram_batch(x, Fs: float, o, out=None, seg_begin: int = 0, seg_end=None, stream=None):
+    """spectral.SpectrogramBatch on a (channels, n) float64 CUDA tensor: the
+    float64 power rows c_j |X|^2 / norm of segments [seg_begin, seg_end) of
+    every channel, as stft_batch (gdsp_spectrogram_batch_device). The mean of
+    all rows of channel c over the segments is pwelch_batch's row c."""
+    return _segment_rows(True, x, Fs, o, out, seg_begin, seg_end, stream)
+
+
 def pwelch_batch(x, Fs: float, o, out=None, acc=None, stream=None):
     """spectral.Pwelch of every row of a (channels, n) float64 CUDA tensor
     (unit inner stride, any row stride), device-resident end to end: returns

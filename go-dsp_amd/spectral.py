@@ -193,6 +193,88 @@ def Coherence(x, y, Fs: float, o: Optional[PwelchOptions]):
     return r.Cxy[0], r.freqs
 
 
+# elements of the device output of one StftBatch / SpectrogramBatch call: longer
+# results are computed as ranges of segments (include/gdsp_fft.h, gdsp_stft_batch)
+STFT_CHUNK_ELEMS = 1 << 25
+
+
+def stft_batch_fused(channels: int, n: int, nfft: int = 0, pad: int = 0,
+                     noverlap: int = 0) -> bool:
+    """Whether per-segment spectra of this shape run the fused kernel over all
+    channels (True) or the materialised form (gdsp_stft_batch_fused)."""
+    return bool(lib().gdsp_stft_batch_fused(int(channels), int(n), int(nfft), int(pad),
+                                            int(noverlap)))
+
+
+def stft_freqs(pad: int, Fs: float) -> np.ndarray:
+    """Pwelch's frequencies of the Pad / 2 + 1 bins (pwelch.go:138-142)."""
+    return np.arange(pad // 2 + 1, dtype=np.float64) * (float(Fs) / float(pad))
+
+
+def stft_times(seg_begin: int, seg_end: int, nfft: int, noverlap: int, Fs: float) -> np.ndarray:
+    """The centres of segments [seg_begin, seg_end) in seconds: (s * stride +
+    NFFT / 2) / Fs, the convention of scipy.signal.spectrogram."""
+    s = np.arange(seg_begin, seg_end, dtype=np.int64) * (nfft - noverlap)
+    return (s.astype(np.float64) + 0.5 * nfft) / float(Fs)
+
+
+def StftBatch(rows, Fs: float, o: Optional[PwelchOptions]):
+    """The short-time Fourier transform of every row of `rows` (equal lengths)
+    in one call (gdsp_stft_batch). Options, segments and the window are
+    Pwelch's. Returns (X[channels, nsegs, lp] complex128, freqs, times): X[c, s]
+    is the first lp = Pad / 2 + 1 bins of the transform of segment s of row c,
+    windowed and zero-padded to max(Pad, NFFT) — pwelch.go:111's pgram —
+    unscaled; times are the segments' centres."""
+    x = _rows(rows)
+    channels, n = x.shape
+    if n == 0:  # pwelch.go:75-77, before the options are looked at
+        return np.zeros((channels, 0, 0), np.complex128), np.zeros(0), np.zeros(0)
+    nfft, pad, noverlap, win_seg, _, lp, _ = _welch_args(o)
+    nsegs = segment_count(max(n, nfft), nfft, noverlap)
+    out = np.empty((channels, nsegs, lp), np.complex128)
+    nso, lpo = _lib._I64(0), _lib._I64(0)
+    check(lib().gdsp_stft_batch(_p(x), channels, n, n, nfft, pad, noverlap, _p(win_seg), _p(out),
+                                nso, lpo), "StftBatch")
+    return out, stft_freqs(pad, Fs), stft_times(0, nsegs, nfft, noverlap, Fs)
+
+
+def SpectrogramBatch(rows, Fs: float, o: Optional[PwelchOptions]):
+    """The spectrogram of every row of `rows` (equal lengths) in one call
+    (gdsp_spectrogram_batch). Returns (P[channels, nsegs, lp] float64, freqs,
+    times): P[c, s, j] = c_j |X[c, s, j]|^2 / norm of StftBatch's X with
+    Pwelch's scaling, so P[c].mean(axis=0) is Pwelch(rows[c], Fs, o)."""
+    x = _rows(rows)
+    channels, n = x.shape
+    if n == 0:  # pwelch.go:75-77, before the options are looked at
+        return np.zeros((channels, 0, 0)), np.zeros(0), np.zeros(0)
+    nfft, pad, noverlap, win_seg, win_nfft, lp, scale_off = _welch_args(o)
+    nsegs = segment_count(max(n, nfft), nfft, noverlap)
+    out = np.empty((channels, nsegs, lp), np.float64)
+    freqs = np.empty(lp, np.float64)
+    times = np.empty(nsegs, np.float64)
+    nso, lpo = _lib._I64(0), _lib._I64(0)
+    check(lib().gdsp_spectrogram_batch(_p(x), channels, n, n, float(Fs), nfft, pad, noverlap,
+                                       _p(win_seg), _p(win_nfft), scale_off, _p(out), _p(freqs),
+                                       _p(times), nso, lpo), "SpectrogramBatch")
+    return out, freqs, times
+
+
+def Stft(x, Fs: float, o: Optional[PwelchOptions]):
+    """The short-time Fourier transform of one signal (MATLAB stft,
+    scipy.signal.stft without its scaling): StftBatch of one row. Returns
+    (X[nsegs, lp], freqs, times)."""
+    X, freqs, times = StftBatch(np.asarray(x, dtype=np.float64).reshape(1, -1), Fs, o)
+    return X[0], freqs, times
+
+
+def Spectrogram(x, Fs: float, o: Optional[PwelchOptions]):
+    """The spectrogram of one signal (MATLAB spectrogram's ps, scipy.signal.
+    spectrogram): SpectrogramBatch of one row. Returns (P[nsegs, lp], freqs,
+    times); P.mean(axis=0) is Pwelch(x, Fs, o)."""
+    P, freqs, times = SpectrogramBatch(np.asarray(x, dtype=np.float64).reshape(1, -1), Fs, o)
+    return P[0], freqs, times
+
+
 def finalize(acc: np.ndarray, nsegs: int, nfft: int, pad: int, win_nfft: np.ndarray, Fs: float,
              scale_off: bool):
     """Host finalisation (gdsp_pwelch_finalize, spectral/pwelch.go:113-142) of

@@ -235,6 +235,29 @@ def PwelchChannels(w: Wav, frames: int, o, Fs: float = 0.0):
     return pxx.cpu().numpy(), freqs
 
 
+def SpectrogramChannels(w: Wav, frames: int, o, Fs: float = 0.0):
+    """The per-channel spectrograms of a multi-channel file: the next `frames`
+    frames of w, decoded planar on the GPU as for PwelchChannels and run
+    through device.spectrogram_batch. Returns (P[NumChannels, nsegs, lp],
+    freqs, times) as numpy arrays; P[c] equals spectral.Spectrogram of channel
+    c's decoded samples, and its mean over the segments PwelchChannels' row c.
+    Fs defaults to w.SampleRate."""
+    import torch
+
+    from . import device
+    spectral.resolve_options(o)
+    C = int(w.NumChannels)
+    raw, _ = w._read_raw(frames * C)
+    if frames == 0:  # pwelch.go:75-77
+        return np.zeros((C, 0, 0)), np.zeros(0), np.zeros(0)
+    fs = float(Fs or w.SampleRate)
+    dev = torch.device("cuda", torch.cuda.current_device())
+    rd = torch.frombuffer(bytearray(raw), dtype=torch.uint8).to(dev)
+    x = device_floats_planar(rd, frames, C, w.AudioFormat, w.BitsPerSample)
+    p, freqs, times = device.spectrogram_batch(x, fs, o)
+    return p.cpu().numpy(), freqs, times
+
+
 def CoherenceChannels(w: Wav, frames: int, o, ref: int = 0, Fs: float = 0.0):
     """The magnitude-squared coherence of every channel of a multi-channel
     file with channel `ref`: the next `frames` frames of w, decoded planar on

@@ -113,7 +113,12 @@ enum {
    * blocks, the plan's batched transform, row multiply, inverse transform,
    * scatter of the valid parts) also for the block lengths the fused
    * overlap-save kernel serves. Read when the call is made. */
-  GDSP_ALGO_NO_FUSED_FIR = 512
+  GDSP_ALGO_NO_FUSED_FIR = 512,
+  /* gdsp_stft_batch / gdsp_spectrogram_batch and their device entries on the
+   * materialised form (gathered real rows, the plan's batched transform, a
+   * kernel that writes the first lp bins or their powers) also for the lengths
+   * the fused per-segment kernel serves. Read when the call is made. */
+  GDSP_ALGO_NO_FUSED_STFT = 1024
 };
 /* Unknown bits → GDSP_ERR_INVALID (the selection is left unchanged). */
 int gdsp_set_algorithm(unsigned flags);
@@ -128,7 +133,8 @@ unsigned gdsp_get_algorithm(void);
  *  - No absolute threshold: inputs times 2^k give outputs times the matching
  *    power of 2 bit for bit (transforms 2^k; Convolve and FIR 2^(a+b) for x
  *    times 2^a and y or h times 2^b; Pwelch 2^2k; cross spectra Pxx 2^2a, Pyy
- *    2^2b, Pxy 2^(a+b), the coherence unchanged), while no intermediate leaves
+ *    2^2b, Pxy 2^(a+b), the coherence unchanged; STFT rows 2^k, spectrogram
+ *    rows 2^2k), while no intermediate leaves
  *    the normal range and, for cross spectra, the two levels stay within the
  *    balance's range (gdsp_cpsd_batch). All-zero inputs give exact zeros.
  *  - A NaN or an infinity in the input makes non-finite exactly what depends
@@ -140,7 +146,9 @@ unsigned gdsp_get_algorithm(void);
  *      cross spectra          all four results of that channel, the other
  *                             signal's P included: one transform carries a
  *                             segment of both signals (a shared y: all channels)
- *      FIR                    outputs [j, j + m) of that row for a bad x[j],
+ *      STFT, spectrogram      every bin of the rows of the segments that hold
+ *                             the sample (tests/test_stft_gpu.py)
+ *      FIR                   outputs [j, j + m) of that row for a bad x[j],
  *                             and possibly more of (j - 2F, j + 2F), F =
  *                             gdsp_fir_block's: a transform carries two blocks
  *                             of F - m + 1 outputs and a sample is read by at
@@ -350,6 +358,60 @@ int gdsp_cpsd_batch(const double *x, int64_t ldx, const double *y, int64_t ldy, 
 int gdsp_cpsd_batch_fused(int64_t channels, int64_t n, int64_t nfft, int64_t pad,
                           int64_t noverlap);
 
+/* Additive per-segment spectra (no reference equivalent; MATLAB stft /
+ * spectrogram, scipy.signal.stft / spectrogram): the quantity gdsp_pwelch
+ * sums away. Options, defaults (nfft 0 = 256, pad 0 = nfft), the zero-padding
+ * of a signal shorter than nfft, the segments (stride = nfft - noverlap),
+ * F = max(pad, nfft), the window win_seg of F entries (NULL = Hann) and
+ * lp = pad/2+1 are gdsp_pwelch's; with pad < nfft a row is the first lp bins
+ * of the F-point transform, as there. With X_s the transform gdsp_pwelch
+ * forms of segment s (windowed, zero-padded to F; spectral/pwelch.go:104-111):
+ *   STFT         out[c][s][j] = X_s[j], complex128, unscaled
+ *   spectrogram  out[c][s][j] = c_j |X_s[j]|^2 / norm, float64, c_j = 2 for
+ *                0 < j < lp-1, else 1; norm = sum win_nfft^2 (times fs unless
+ *                scale_off), in gdsp_pwelch_finalize's order (the square sum,
+ *                the doubling, the division), so the mean of the rows over s
+ *                is gdsp_pwelch's pxx
+ * for channel c at x + c*ldx, s < nsegs = gdsp_segment_count(max(n, nfft),
+ * nfft, noverlap), j < lp: out is channels × nsegs × lp, dense. freqs[j] =
+ * j*fs/pad (lp float64), times[s] = (s*stride + nfft/2)/fs (nsegs float64:
+ * the segment's centre, scipy.signal.spectrogram's convention).
+ * The imaginary parts of bins 0 and F/2 are exact zeros.
+ * Accuracy: the fused kernel packs two segments into one transform (z = w x_s
+ * + i a w x_(s+1)), whose roundoff is relative to the larger of the two. a is
+ * a power of 2 from the binary exponents of the two segments' maxima, taken
+ * out of segment s+1's row again, exactly (the balance of gdsp_cpsd_batch,
+ * its range and its exceptions): a quiet segment beside a loud one keeps its
+ * digits in its own row. A segment of all zeros gives a row of exact zeros. A
+ * NaN or an infinity makes non-finite the rows of the segments that contain
+ * it and changes no other row by a bit: a group of pairs that holds one runs
+ * its even and its odd segments in transforms of their own. Inputs times 2^k
+ * give STFT rows times 2^k and spectrogram rows times 2^2k bit for bit.
+ * Before any device call: a NULL nsegs_out or lp_out, or a needed NULL x, out,
+ * freqs or times, channels < 0, n < 0, nfft < 0, pad < 0, ldx < n with
+ * channels > 1 → GDSP_ERR_INVALID; a zero stride → GDSP_ERR_DIVIDE_BY_ZERO
+ * as from gdsp_segment_count. n == 0 → *nsegs_out = *lp_out = 0, GDSP_OK;
+ * channels == 0 → only freqs, times and the counts are written. The device
+ * output is held to 2^25 elements (512 MiB of complex128): longer results
+ * run as ranges of segments that begin at even indices, so no bit of a row
+ * depends on where a range was cut. F a power of 2 from 64 to 2048 runs one
+ * fused kernel over all channels (gdsp_stft_batch_fused); every other length
+ * the materialised form. Runs on the current device. */
+int gdsp_stft_batch(const double *x, int64_t channels, int64_t n, int64_t ldx, int64_t nfft,
+                    int64_t pad, int64_t noverlap, const double *win_seg, double *out,
+                    int64_t *nsegs_out, int64_t *lp_out);
+int gdsp_spectrogram_batch(const double *x, int64_t channels, int64_t n, int64_t ldx, double fs,
+                           int64_t nfft, int64_t pad, int64_t noverlap, const double *win_seg,
+                           const double *win_nfft, int scale_off, double *out, double *freqs,
+                           double *times, int64_t *nsegs_out, int64_t *lp_out);
+/* 1: a call of gdsp_stft_batch, gdsp_spectrogram_batch or their device
+ * entries of this shape (0 = the defaults) runs the fused kernel under the
+ * current flags; 0: the materialised form (F < 64, F = 4096 and up,
+ * non-powers of 2, strides above 2^22, GDSP_ALGO_NO_FUSED_STFT). Host
+ * arithmetic only (no GPU needed), as gdsp_cpsd_batch_fused. */
+int gdsp_stft_batch_fused(int64_t channels, int64_t n, int64_t nfft, int64_t pad,
+                          int64_t noverlap);
+
 /* window.Hann — window/window.go:62-76, as a host table generator used by the
  * shim for the default window (L float64 written to out). */
 int gdsp_window_hann(int64_t L, double *out);
@@ -403,10 +465,12 @@ int gdsp_multi_stats(int64_t *batch_calls, int64_t *pwelch_calls, int64_t *rccl_
  * iterations of the host loops that cut one call into several launches (the
  * materialised Pwelch's pair chunks and Cpsd's channel and segment runs, the
  * channels-per-launch loops of the fused batched Pwelch and Cpsd, the channel
- * loop of the batched Pwelch where it has no fused kernel, the composed FIR's
+ * loop of the batched Pwelch where it has no fused kernel, the segment ranges
+ * of gdsp_stft_batch / gdsp_spectrogram_batch and the channel and segment runs
+ * of their materialised form, the composed FIR's
  * transform chunks, and the 65535-row pieces of gdsp_fft_axis_device /
  * gdsp_fftn_device and of the multi-pass, four-step and chirp-z executors).
- * multi_unit_launches: launches of a Pwelch, batched-Pwelch or Cpsd kernel
+ * multi_unit_launches: launches of a Pwelch, batched-Pwelch, Cpsd or STFT kernel
  * whose persistent workers each take at least two pairs (or pair groups). A
  * test reads both before and after a call to prove that the call reached the
  * path it was shaped for. Any pointer may be NULL. */
@@ -619,6 +683,33 @@ int gdsp_cpsd_batch_finalize_device(const double *d_acc, int64_t channels, int64
                                     const double *win_nfft, double fs, int scale_off,
                                     void *d_pxy, double *d_pxx, double *d_pyy, double *d_coh,
                                     double *freqs, void *stream);
+
+/* gdsp_stft_batch on device buffers: the rows of segments [seg_begin,
+ * seg_end) of every channel (channel c: n float64 at d_x + c*ldx) into d_out,
+ * complex128; row (c, s) at element c*ld_chan + (s - seg_begin)*ld_seg, its
+ * lp = pad/2+1 bins contiguous. The strides are the caller's, in elements of
+ * the output type: ld_seg >= lp and, with channels > 1, ld_chan >= (seg_end -
+ * seg_begin)*ld_seg; nothing between the rows is written. d_win_seg: the
+ * window of max(pad, nfft) on the device. A range that begins at an odd
+ * segment pairs the segments differently in the fused kernel, so its rows
+ * agree with the whole call's to roundoff, not bit for bit; a range that
+ * begins at an even one gives the same bits. nfft <= 0, pad <= 0, a negative
+ * or reversed range, channels < 0, n < 0, ldx < n with channels > 1, ld_seg <
+ * lp, ld_chan too small, a needed NULL pointer, or seg_end past the signal →
+ * GDSP_ERR_INVALID; nfft == noverlap with seg_end > 1 →
+ * GDSP_ERR_DIVIDE_BY_ZERO; all before any device call. channels == 0 or an
+ * empty range: nothing is written, GDSP_OK. */
+int gdsp_stft_batch_device(const double *d_x, int64_t ldx, int64_t channels, int64_t n,
+                           int64_t nfft, int64_t pad, int64_t noverlap, int64_t seg_begin,
+                           int64_t seg_end, const double *d_win_seg, void *d_out, int64_t ld_seg,
+                           int64_t ld_chan, void *stream);
+/* The same for gdsp_spectrogram_batch: float64 rows c_j |X_s[j]|^2 / norm;
+ * norm as gdsp_spectrogram_batch forms it (1: the raw c_j |X|^2), the
+ * divisor as it is given. */
+int gdsp_spectrogram_batch_device(const double *d_x, int64_t ldx, int64_t channels, int64_t n,
+                                  int64_t nfft, int64_t pad, int64_t noverlap, int64_t seg_begin,
+                                  int64_t seg_end, const double *d_win_seg, double norm,
+                                  double *d_out, int64_t ld_seg, int64_t ld_chan, void *stream);
 
 /* gdsp_wav_read_floats_device for a multi-channel data chunk, into planar
  * float64 rows: d_out[c*ld_out + i] = the widened float32 of sample c of
