@@ -94,6 +94,11 @@ SIGNATURES = {
                                     _I64, _I64, _P]),
     "gdsp_spectrogram_batch_device": (_I, [_P, _I64, _I64, _I64, _I64, _I64, _I64, _I64, _I64, _P,
                                            _D, _P, _I64, _I64, _P]),
+    "gdsp_istft_batch": (_I, [_P, _I64, _I64, _I64, _I64, _I64, _P, _I64, _P, _I64,
+                              ctypes.POINTER(_I64)]),
+    "gdsp_istft_batch_fused": (_I, [_I64, _I64, _I64, _I64, _I64]),
+    "gdsp_istft_batch_device": (_I, [_P, _I64, _I64, _I64, _I64, _I64, _I64, _I64, _I64, _I64, _P,
+                                     _I64, _I64, _P, _I64, _P]),
     "gdsp_wav_read_floats_planar_device": (_I, [_P, _I64, _I64, _I, _I, _P, _I64, _P]),
     "gdsp_window_hann": (_I, [_I64, _P]),
     "gdsp_plan_create": (_I, [_I64, ctypes.POINTER(_P)]),

@@ -1,7 +1,7 @@
 // api_internal.hpp — the host vocabulary the translation units of the C ABI
 // share: gdsp_api.hip (streams, staging, workspaces, executors, the FFT,
 // Convolve and FIR entries), welch.hip (the Welch family: Pwelch, batched
-// Pwelch, Cpsd, STFT), plan.hip (the planner) and multi.hip (the multi-device
+// Pwelch, Cpsd, STFT, ISTFT), plan.hip (the planner) and multi.hip (the multi-device
 // layer). Not part of the C ABI.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -47,7 +47,7 @@ enum Slot {
   SLOT_IN = 0, SLOT_OUT, SLOT_AUX, SLOT_AUX2, SLOT_GLOBAL, SLOT_GLOBAL_IN, SLOT_REAL,
   SLOT_BLU, SLOT_FFT2, SLOT_PW_PART, SLOT_PW_RED, SLOT_PW_BUF, SLOT_FS0, SLOT_FS1, SLOT_FS2,
   SLOT_FS3, SLOT_FFTN, SLOT_MX0, SLOT_MX1, SLOT_PARTS, SLOT_CONV, SLOT_CP_Y, SLOT_CP_OUT, SLOT_CP_BAL,
-  SLOT_FIR, SLOT_FIR_H, SLOT_FIR_OUT, SLOT_ST_ROWS, SLOT_ST_OUT,
+  SLOT_FIR, SLOT_FIR_H, SLOT_FIR_OUT, SLOT_ST_ROWS, SLOT_ST_OUT, SLOT_IS_D,
   SLOT_COUNT
 };
 
@@ -76,7 +76,7 @@ int run_queued(hipStream_t s, F &&queue) {
 
 // Counters of gdsp_loop_stats. A host chunk loop calls later_chunk(i0) in
 // every iteration: the second and later ones (i0 > 0) count. multi_unit(u)
-// stands before a launch of a Pwelch, batched-Pwelch, Cpsd or STFT kernel
+// stands before a launch of a Pwelch, batched-Pwelch, Cpsd, STFT or ISTFT kernel
 // whose workers take u pairs or groups each: u >= 2 counts.
 void later_chunk(int64_t i0);
 void multi_unit(int64_t units);

@@ -139,6 +139,39 @@ hipError_t launch_stft_gather(const double *x, int64_t ldx, int64_t channels, in
 hipError_t launch_stft_rows(const cd *buf, int64_t channels, int64_t ns, int64_t flen, int64_t lp,
                             bool power, double norm, void *out, int64_t row0, int64_t ld_seg,
                             int64_t ld_chan, hipStream_t s);
+// the overlap-add inverse of those rows (istft_batch.hip): out[c ldo + i -
+// out_begin] = num[i] / D[i] (exactly 0 where D[i] == 0) for out_begin <= i <
+// out_end, num and D summed over the segments that cover i in ascending s. X
+// holds rows [row_lo, row_hi) of every channel, row (c, s) at c ld_chan + (s -
+// row_lo) ld_seg; rows outside are neither read nor used. The fused kernel
+// (F = 2^log2f from 64 to 2048 = pad, 0 < stride <= nfft <= 4 stride): groups
+// of istft_group_segments(log2f) segments aligned by absolute index, group g
+// owning samples [g, g + 1) * that * stride; groups [g_begin, g_end) over wpc
+// workers per channel of gpw groups each (istft_batch_geometry), every worker
+// recomputing its halo; dtab from launch_istft_dtable (istft_dtable_doubles
+// (stride) doubles). The materialised form: launch_istft_complete writes the
+// dense Hermitian rows of segments [seg0, seg0 + ns) of nc channels (buf row
+// c ns + j), and after the plan's inverse transform launch_istft_ola sums
+// samples [i0, i1) with one thread each from those rows.
+bool istft_batch_applies(int log2f);
+int istft_group_segments(int log2f);
+void istft_batch_geometry(int log2f, int64_t channels, int64_t ngroups, int halo_groups,
+                          int64_t *wpc, int64_t *gpw);
+int64_t istft_dtable_doubles(int64_t stride);
+hipError_t launch_istft_dtable(const double *win, int64_t nfft, int64_t stride, int64_t nsegs,
+                               double *dtab, hipStream_t s);
+hipError_t launch_istft_batch(int log2f, const cd *X, int64_t ld_seg, int64_t ld_chan,
+                              int64_t channels, int64_t nsegs, int64_t row_lo, int64_t row_hi,
+                              int64_t nfft, int64_t stride, int64_t g_begin, int64_t g_end,
+                              int64_t wpc, int64_t gpw, const double *win, const double *dtab,
+                              const cd *tw, int64_t out_begin, int64_t out_end, double *out,
+                              int64_t ldo, hipStream_t s);
+hipError_t launch_istft_complete(const cd *X, int64_t ld_seg, int64_t ld_chan, int64_t row_lo,
+                                 int64_t nc, int64_t seg0, int64_t ns, int64_t flen, cd *buf,
+                                 hipStream_t s);
+hipError_t launch_istft_ola(const cd *buf, int64_t nc, int64_t seg0, int64_t ns, int64_t nsegs,
+                            int64_t flen, int64_t nfft, int64_t stride, const double *win,
+                            int64_t i0, int64_t i1, double *out, int64_t ldo, hipStream_t s);
 // fused Pwelch on a compiled specialisation (d = the plan's specialisation
 // descriptor, d.n = max(pad, nfft)); workers per block, 0 if d is none or
 // its kernel cannot stage a pair of span = stride + nfft samples

@@ -1,9 +1,10 @@
 // welch.hip — the Welch family of the C ABI (include/gdsp_fft.h): Pwelch, the
 // batched Pwelch over the channels of a planar batch, the batched cross
-// spectra (Cpsd, coherence) and the per-segment spectra (STFT, spectrogram);
-// with them spectral.Segment's count and the Hann table. Host arithmetic only:
-// the kernels are in pwelch_*.hip, cpsd_batch.hip, stft_batch.hip and the
-// transform files, behind launch.hpp.
+// spectra (Cpsd, coherence), the per-segment spectra (STFT, spectrogram) and
+// their overlap-add inverse (ISTFT); with them spectral.Segment's count and
+// the Hann table. Host arithmetic only: the kernels are in pwelch_*.hip,
+// cpsd_batch.hip, stft_batch.hip, istft_batch.hip and the transform files,
+// behind launch.hpp.
 #include <math.h>
 
 #include <string>
@@ -299,6 +300,203 @@ int stft_host(bool power, const double *x, int64_t channels, int64_t n, int64_t 
     // channel c's rows [s0, s0 + ns): dense on the device, nsegs rows apart on the host
     STCHK(unstage_rows(out + s0 * w.lp * dpe, (const double *)dout.p, channels, ns * w.lp * dpe,
                        w.nsegs * w.lp * dpe, s));
+  }
+  return GDSP_OK;
+}
+
+// ---- the overlap-add inverse of the STFT rows ----------------------------------
+
+// complex elements of a host call's device copy of X, and of a materialised
+// chunk's dense rows: 512 MiB of complex128, a constant of this entry
+constexpr int64_t kIstftChunkElems = (int64_t)1 << 25;
+
+// The fused kernel (istft_batch.hip) serves F = Pad of the batched kernels'
+// lengths with 0 < stride <= NFFT <= 4 stride: at most 4 segments over a
+// sample, no gaps between segments (a negative Noverlap would make the D table
+// as long as the gaps).
+bool istft_batch_fused(int64_t nfft, int64_t pad, int64_t stride) {
+  return pad >= nfft && stride >= 1 && stride <= nfft && nfft <= 4 * stride &&
+         batch_fused(pad, stride, gdsp::istft_batch_applies, GDSP_ALGO_NO_FUSED_ISTFT);
+}
+
+// the first and the last segment that cover a sample of [i0, i1)
+void istft_cover(int64_t i0, int64_t i1, int64_t nsegs, int64_t nfft, int64_t stride,
+                 int64_t *slo, int64_t *shi) {
+  *slo = i0 >= nfft ? (i0 - nfft) / stride + 1 : 0;
+  *shi = (i1 - 1) / stride;
+  if (*shi > nsegs - 1) *shi = nsegs - 1;
+}
+
+// gdsp_istft_batch_device
+int istft_device(const void *d_X, int64_t ld_seg, int64_t ld_chan, int64_t channels,
+                 int64_t nsegs, int64_t seg_row0, int64_t seg_rows, int64_t nfft, int64_t pad,
+                 int64_t noverlap, const double *d_win_seg, int64_t out_begin, int64_t out_end,
+                 double *d_out, int64_t ldo, void *stream) {
+  if (nfft <= 0 || pad < nfft) return fail(GDSP_ERR_INVALID, "bad ISTFT geometry: Pad below NFFT");
+  if (channels < 0 || nsegs < 0 || seg_row0 < 0 || seg_rows < 0 || seg_rows > nsegs ||
+      seg_row0 > nsegs - seg_rows)
+    return fail(GDSP_ERR_INVALID, "bad batch geometry");
+  if (out_begin < 0 || out_end < out_begin) return fail(GDSP_ERR_INVALID, "bad sample range");
+  const int64_t lp = pad / 2 + 1, len = out_end - out_begin;
+  if (ld_seg < lp || (channels > 1 && seg_rows > 0 && ld_chan / seg_rows < ld_seg))
+    return fail(GDSP_ERR_INVALID, "input strides below the rows");
+  if (channels > 1 && ldo < len) return fail(GDSP_ERR_INVALID, "ldo below the range");
+  int64_t stride = nfft - noverlap;
+  if (stride == 0 && nsegs > 1) return fail(GDSP_ERR_DIVIDE_BY_ZERO, "integer divide by zero");
+  if (stride < 0 && nsegs > 1) return fail(GDSP_ERR_INVALID, "a negative stride");
+  if (nsegs == 0) {
+    if (len > 0) return fail(GDSP_ERR_INVALID, "sample range past the signal");
+    return GDSP_OK;
+  }
+  const bool fused = istft_batch_fused(nfft, pad, stride);
+  if (nsegs == 1 && stride < 1) stride = nfft;  // one segment: the stride places nothing
+  if (stride > (INT64_MAX - nfft) / nsegs) return fail(GDSP_ERR_INVALID, "signal length overflows");
+  const int64_t n_full = (nsegs - 1) * stride + nfft;
+  if (out_end > n_full) return fail(GDSP_ERR_INVALID, "sample range past the signal");
+  if (channels == 0 || len == 0) return GDSP_OK;
+  if (!d_X || !d_win_seg || !d_out) return fail(GDSP_ERR_INVALID, "NULL pointer");
+  int64_t slo = 0, shi = 0;
+  istft_cover(out_begin, out_end, nsegs, nfft, stride, &slo, &shi);
+  // a range inside a gap between segments (a negative Noverlap) needs no row
+  const bool covered = slo <= shi;
+  if (covered && fused) {
+    // the fused kernel transforms rows (2p, 2p + 1) together: a row's bits
+    // depend on its partner, so the range's rows are needed as whole pairs
+    slo &= ~(int64_t)1;
+    if (shi + 1 < nsegs) shi |= 1;
+  }
+  if (covered && (slo < seg_row0 || shi >= seg_row0 + seg_rows))
+    return fail(GDSP_ERR_INVALID, fused ? "rows of the range are missing (whole pairs are needed)"
+                                        : "rows of the range are missing");
+  hipStream_t s = (hipStream_t)stream;
+  gdsp_plan *p = nullptr;
+  STCHK(get_plan(pad, &p));
+  if (fused && p->kind == KIND_LDS) {
+    const int64_t owned = gdsp::istft_group_segments(p->log2n) * stride;
+    const int64_t g_begin = out_begin / owned, g_end = (out_end - 1) / owned + 1;
+    const int halo = (int)((nfft - stride + owned - 1) / owned);
+    int64_t wpc = 0, gpw = 0;
+    gdsp::istft_batch_geometry(p->log2n, channels, g_end - g_begin, halo, &wpc, &gpw);
+    DevBuf dtab;
+    STCHK(dtab.alloc((size_t)gdsp::istft_dtable_doubles(stride) * sizeof(double), s, SLOT_IS_D));
+    HIPCHK(gdsp::launch_istft_dtable(d_win_seg, nfft, stride, nsegs, (double *)dtab.p, s));
+    multi_unit(gpw);
+    HIPCHK(gdsp::launch_istft_batch(p->log2n, (const cd *)d_X, ld_seg, ld_chan, channels, nsegs,
+                                    seg_row0, seg_row0 + seg_rows, nfft, stride, g_begin, g_end,
+                                    wpc, gpw, d_win_seg, (const double *)dtab.p, p->tw, out_begin,
+                                    out_end, d_out, ldo, s));
+    return GDSP_OK;
+  }
+  // materialised form: chunks of at most 512 MiB of dense complex rows, whole
+  // channels where the rows of a channel's range fit, else one channel's range
+  // in runs of samples, each with the rows that reach into it (its halo)
+  int64_t maxrows = kIstftChunkElems / pad;
+  const int64_t reach = (nfft + stride - 1) / stride;  // segments over a sample
+  if (maxrows < reach + 1) maxrows = reach + 1;
+  const int64_t need = covered ? shi - slo + 1 : 1;
+  int64_t cpl = 1, run = len;  // channels per launch, samples per run
+  if (need <= maxrows) {
+    cpl = maxrows / need < channels ? maxrows / need : channels;
+  } else {
+    run = (maxrows - reach) * stride;
+  }
+  const int64_t ns_max = need <= maxrows ? need : maxrows;
+  DevBuf buf;
+  STCHK(buf.alloc((size_t)cpl * (size_t)ns_max * (size_t)pad * sizeof(cd), s, SLOT_PW_BUF));
+  const cd *const X = (const cd *)d_X;
+  for (int64_t c0 = 0; c0 < channels; c0 += cpl) {
+    const int64_t nc = channels - c0 < cpl ? channels - c0 : cpl;
+    later_chunk(c0);
+    for (int64_t i0 = out_begin; i0 < out_end; i0 += run) {
+      const int64_t i1 = out_end - i0 < run ? out_end : i0 + run;
+      later_chunk(i0 - out_begin);
+      int64_t a = 0, b = 0;
+      istft_cover(i0, i1, nsegs, nfft, stride, &a, &b);
+      const int64_t ns = b - a + 1;
+      double *const o = d_out + c0 * ldo + (i0 - out_begin);
+      if (ns < 1) {  // a run inside a gap between segments: D == 0, exact zeros
+        HIPCHK(hipMemset2DAsync(o, (size_t)ldo * sizeof(double), 0,
+                                (size_t)(i1 - i0) * sizeof(double), (size_t)nc, s));
+        continue;
+      }
+      HIPCHK(gdsp::launch_istft_complete(X + c0 * ld_chan, ld_seg, ld_chan, seg_row0, nc, a, ns,
+                                         pad, (cd *)buf.p, s));
+      STCHK(exec_plan(p, buf.p, (cd *)buf.p, nc * ns, true, gdsp::LOAD_COMPLEX, s));
+      HIPCHK(gdsp::launch_istft_ola((const cd *)buf.p, nc, a, ns, nsegs, pad, nfft, stride,
+                                    d_win_seg, i0, i1, o, ldo, s));
+    }
+  }
+  return GDSP_OK;
+}
+
+// gdsp_istft_batch: X is channels x nsegs x lp, dense. The device copy of X
+// holds at most kIstftChunkElems elements: output ranges that begin at
+// multiples of 2 stride (whole pairs of the fused kernel), each uploaded with
+// the pairs that reach into it, each range copied back before the next.
+int istft_host(const void *X, int64_t channels, int64_t nsegs, int64_t nfft, int64_t pad,
+               int64_t noverlap, const double *win_seg, int64_t n, double *out, int64_t ldo,
+               int64_t *n_out) {
+  if (!n_out) return fail(GDSP_ERR_INVALID, "NULL pointer");
+  *n_out = 0;
+  if (channels < 0 || nsegs < 0 || n < 0) return fail(GDSP_ERR_INVALID, "negative size");
+  if (!welch_defaults(&nfft, &pad)) return fail(GDSP_ERR_INVALID, "negative NFFT/Pad");
+  if (nfft == 0 || pad < nfft) return fail(GDSP_ERR_INVALID, "Pad below NFFT has no inverse");
+  int64_t stride = nfft - noverlap;
+  if (stride == 0 && nsegs > 1) return fail(GDSP_ERR_DIVIDE_BY_ZERO, "integer divide by zero");
+  if (stride < 0 && nsegs > 1) return fail(GDSP_ERR_INVALID, "a negative stride");
+  if (nsegs == 0) return n > 0 ? fail(GDSP_ERR_INVALID, "n past the signal") : GDSP_OK;
+  if (nsegs == 1 && stride < 1) stride = nfft;
+  if (stride > (INT64_MAX - nfft) / nsegs) return fail(GDSP_ERR_INVALID, "signal length overflows");
+  const int64_t n_full = (nsegs - 1) * stride + nfft;
+  if (n > n_full) return fail(GDSP_ERR_INVALID, "n past the signal");
+  if (n == 0) n = n_full;
+  if (channels > 1 && ldo < n) return fail(GDSP_ERR_INVALID, "ldo below the row length");
+  if (channels > 0 && (!X || !out)) return fail(GDSP_ERR_INVALID, "NULL pointer");
+  *n_out = n;
+  if (channels == 0) return GDSP_OK;
+  const int64_t lp = pad / 2 + 1;
+  std::vector<double> hseg;
+  win_seg = hann_or(win_seg, pad, hseg);
+  int dev = 0;
+  STCHK(current_device(&dev));
+  hipStream_t s = thread_stream(dev);
+  if (!s) return fail(GDSP_ERR_HIP, "stream creation failed");
+  // rows per range: the range's own pairs and the two pairs before them
+  const int64_t reach = (nfft + stride - 1) / stride;
+  const int64_t halo = (reach + 1) & ~(int64_t)1;
+  const int64_t fit = kIstftChunkElems / (channels * lp);
+  int64_t per = nsegs, rows_max = nsegs;  // new rows per range, rows on the device
+  if (fit < nsegs) {
+    per = (fit - halo - 2) & ~(int64_t)1;
+    if (per < 2) per = 2;
+    rows_max = per + halo + 2 < nsegs ? per + halo + 2 : nsegs;
+  }
+  const int64_t span = per >= nsegs ? n : per * stride;  // samples per range
+  DevBuf dx, dw, dout;
+  STCHK(dx.alloc((size_t)channels * (size_t)rows_max * (size_t)lp * sizeof(cd), s, SLOT_IN));
+  STCHK(dw.alloc((size_t)pad * sizeof(double), s, SLOT_AUX));
+  STCHK(dout.alloc((size_t)channels * (size_t)(span < n ? span : n) * sizeof(double), s,
+                   SLOT_ST_OUT));
+  const cd *const hx = (const cd *)X;
+  for (int64_t i0 = 0; i0 < n; i0 += span) {
+    const int64_t i1 = n - i0 < span ? n : i0 + span;
+    later_chunk(i0);
+    int64_t a = 0, b = 0;
+    istft_cover(i0, i1, nsegs, nfft, stride, &a, &b);
+    if (b < a) b = a;  // a range inside a gap: no row is needed, one is passed
+    a &= ~(int64_t)1;  // whole pairs
+    if (b + 1 < nsegs && !(b & 1)) ++b;
+    const int64_t nr = b - a + 1;
+    if (nr > rows_max) return fail(GDSP_ERR_INVALID, "internal: ISTFT range rows");
+    STCHK(run_queued(s, [&]() -> int {
+      if (i0 == 0) STCHK(copy_h2d(dw.p, win_seg, (size_t)pad * sizeof(double), s));
+      for (int64_t c = 0; c < channels; ++c)
+        STCHK(copy_h2d((cd *)dx.p + c * nr * lp, hx + (c * nsegs + a) * lp,
+                       (size_t)nr * (size_t)lp * sizeof(cd), s));
+      return istft_device(dx.p, lp, nr * lp, channels, nsegs, a, nr, nfft, pad, noverlap,
+                          (const double *)dw.p, i0, i1, (double *)dout.p, i1 - i0, s);
+    }));
+    STCHK(unstage_rows(out + i0, (const double *)dout.p, channels, i1 - i0, ldo, s));
   }
   return GDSP_OK;
 }
@@ -810,6 +1008,29 @@ int gdsp_spectrogram_batch(const double *x, int64_t channels, int64_t n, int64_t
                            double *times, int64_t *nsegs_out, int64_t *lp_out) {
   return stft_host(true, x, channels, n, ldx, fs, nfft, pad, noverlap, win_seg, win_nfft,
                    scale_off, out, freqs, times, nsegs_out, lp_out);
+}
+
+// ---- the overlap-add inverse of the STFT rows ----------------------------------
+
+int gdsp_istft_batch_fused(int64_t channels, int64_t nsegs, int64_t nfft, int64_t pad,
+                           int64_t noverlap) {
+  if (channels < 0 || nsegs < 0 || !welch_defaults(&nfft, &pad)) return 0;
+  return istft_batch_fused(nfft, pad, nfft - noverlap) ? 1 : 0;
+}
+
+int gdsp_istft_batch_device(const void *d_X, int64_t ld_seg, int64_t ld_chan, int64_t channels,
+                            int64_t nsegs, int64_t seg_row0, int64_t seg_rows, int64_t nfft,
+                            int64_t pad, int64_t noverlap, const double *d_win_seg,
+                            int64_t out_begin, int64_t out_end, double *d_out, int64_t ldo,
+                            void *stream) {
+  return istft_device(d_X, ld_seg, ld_chan, channels, nsegs, seg_row0, seg_rows, nfft, pad,
+                      noverlap, d_win_seg, out_begin, out_end, d_out, ldo, stream);
+}
+
+int gdsp_istft_batch(const void *X, int64_t channels, int64_t nsegs, int64_t nfft, int64_t pad,
+                     int64_t noverlap, const double *win_seg, int64_t n, double *out, int64_t ldo,
+                     int64_t *n_out) {
+  return istft_host(X, channels, nsegs, nfft, pad, noverlap, win_seg, n, out, ldo, n_out);
 }
 
 }  // extern "C"

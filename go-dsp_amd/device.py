@@ -444,6 +444,58 @@ def spectrogram_batch(x, Fs: float, o, out=None, seg_begin: int = 0, seg_end=Non
     return _segment_rows(True, x, Fs, o, out, seg_begin, seg_end, stream)
 
 
+def istft_batch(X, o, out=None, n=None, out_begin: int = 0, out_end=None, stream=None):
+    """spectral.IstftBatch on a (channels, nsegs, pad // 2 + 1) complex128 CUDA
+    tensor, device-resident (gdsp_istft_batch_device): samples [out_begin,
+    out_end) (None: n, itself None for all (nsegs - 1) * stride + nfft) of
+    every channel, as a (channels, out_end - out_begin) float64 tensor. X may
+    be any view whose last dimension is contiguous; out any view of the
+    result's shape with unit inner stride: nothing between its rows is written.
+    Every range gives the bits of the whole call."""
+    import contextlib
+
+    from . import distributed, spectral
+    torch = _torch()
+    assert X.is_cuda and X.dtype == torch.complex128 and X.dim() == 3
+    channels, nsegs, lpx = X.shape
+    dev = X.device
+    if nsegs == 0 or lpx == 0:
+        return torch.zeros((channels, 0), dtype=torch.float64, device=dev)
+    nfft, pad, noverlap, wf, _ = spectral.resolve_options(o)
+    if pad < nfft:
+        raise _lib.Panic(_lib.GDSP_ERR_INVALID,
+                         "Pad below NFFT: a truncated spectrum has no inverse")
+    lp = pad // 2 + 1
+    if lpx != lp:
+        raise _lib.Panic(_lib.GDSP_ERR_INVALID,
+                         "rows of %d bins, Pad / 2 + 1 = %d expected" % (lpx, lp))
+    assert X.stride(2) == 1, "rows must have unit inner stride"
+    n_full = spectral.istft_length(nsegs, nfft, noverlap) if nsegs > 1 else nfft
+    n = n_full if n is None else int(n)
+    out_end = n if out_end is None else int(out_end)
+    out_begin = int(out_begin)
+    assert 0 <= out_begin <= out_end <= n <= n_full, (out_begin, out_end, n, n_full)
+    length = out_end - out_begin
+    ctx = torch.cuda.stream(stream) if stream is not None else contextlib.nullcontext()
+    with torch.cuda.device(dev), ctx:
+        if out is None:
+            out = torch.empty((channels, length), dtype=torch.float64, device=dev)
+        assert out.is_cuda and out.dtype == torch.float64 and out.device == dev
+        assert tuple(out.shape) == (channels, length), (tuple(out.shape), (channels, length))
+        assert length <= 1 or out.stride(1) == 1, "rows must have unit inner stride"
+        if channels == 0 or length == 0:
+            return out
+        ld_seg = X.stride(1) if nsegs > 1 else lp
+        ld_chan = X.stride(0) if channels > 1 else nsegs * ld_seg
+        ldo = out.stride(0) if channels > 1 else length
+        win_seg = distributed._device_window(wf, pad, dev, torch)
+        check(lib().gdsp_istft_batch_device(
+            _ptr(X), ld_seg, ld_chan, channels, nsegs, 0, nsegs, nfft, pad, noverlap,
+            _ptr(win_seg), out_begin, out_end, _ptr(out), ldo, _stream_ptr(stream, dev)),
+            "istft_batch_device")
+    return out
+
+
 def pwelch_batch(x, Fs: float, o, out=None, acc=None, stream=None):
     """spectral.Pwelch of every row of a (channels, n) float64 CUDA tensor
     (unit inner stride, any row stride), device-resident end to end: returns

@@ -300,6 +300,7 @@ ALGO_NO_FUSED_PWELCH_BATCH = 128
 ALGO_NO_FUSED_CPSD = 256
 ALGO_NO_FUSED_FIR = _lib.GDSP_ALGO_NO_FUSED_FIR
 ALGO_NO_FUSED_STFT = 1024
+ALGO_NO_FUSED_ISTFT = 4096  # 2048 is not a flag
 
 
 def SetAlgorithm(flags: int = ALGO_DEFAULT) -> None:
@@ -324,7 +325,7 @@ def MultiStats() -> dict:
 
 def LoopStats() -> dict:
     """gdsp_loop_stats: second-or-later iterations of the host chunk loops, and
-    Pwelch / Cpsd / STFT launches whose workers took two or more pairs or groups,
+    Pwelch / Cpsd / STFT / ISTFT launches whose workers took two or more pairs or groups,
     since process start."""
     import ctypes
     v = [ctypes.c_int64() for _ in range(2)]

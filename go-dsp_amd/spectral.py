@@ -267,6 +267,69 @@ def Stft(x, Fs: float, o: Optional[PwelchOptions]):
     return X[0], freqs, times
 
 
+# complex elements of the device copy of X in one IstftBatch call: longer inputs
+# are inverted as ranges of samples (include/gdsp_fft.h, gdsp_istft_batch)
+ISTFT_CHUNK_ELEMS = 1 << 25
+
+
+def istft_batch_fused(channels: int, nsegs: int, nfft: int = 0, pad: int = 0,
+                      noverlap: int = 0) -> bool:
+    """Whether the inverse of per-segment spectra of this shape runs the fused
+    overlap-add kernel (True) or the materialised form (gdsp_istft_batch_fused)."""
+    return bool(lib().gdsp_istft_batch_fused(int(channels), int(nsegs), int(nfft), int(pad),
+                                             int(noverlap)))
+
+
+def istft_length(nsegs: int, nfft: int, noverlap: int) -> int:
+    """The samples nsegs segments span: (nsegs - 1) * stride + NFFT (0: none)."""
+    return (nsegs - 1) * (nfft - noverlap) + nfft if nsegs > 0 else 0
+
+
+def IstftBatch(X, o: Optional[PwelchOptions], n: Optional[int] = None):
+    """The inverse of StftBatch by weighted overlap-add (gdsp_istft_batch;
+    MATLAB istft, scipy.signal.istft): X[channels, nsegs, Pad / 2 + 1]
+    complex128 -> rows[channels, n], n = (nsegs - 1) * stride + NFFT unless a
+    shorter n is given. rows[c, i] = sum_s w y_s / sum_s w^2 over the segments
+    that cover i, exactly 0 where the window leaves a sample without weight.
+    Pad >= NFFT is required."""
+    X = np.asarray(X)
+    if X.ndim != 3:
+        raise Panic(_lib.GDSP_ERR_INVALID, "X must be channels x nsegs x (Pad/2+1)")
+    channels, nsegs = X.shape[:2]
+    if nsegs == 0 or X.shape[2] == 0:  # what StftBatch returns for an empty signal
+        return np.zeros((channels, 0))
+    nfft, pad, noverlap, win_seg, _, lp, _ = _welch_args(o)
+    if pad < nfft:
+        raise Panic(_lib.GDSP_ERR_INVALID, "Pad below NFFT: a truncated spectrum has no inverse")
+    if X.shape[2] != lp:
+        raise Panic(_lib.GDSP_ERR_INVALID,
+                    "rows of %d bins, Pad / 2 + 1 = %d expected" % (X.shape[2], lp))
+    X = np.ascontiguousarray(X, dtype=np.complex128)
+    if nfft == noverlap and nsegs > 1:
+        raise Panic(_lib.GDSP_ERR_DIVIDE_BY_ZERO, "runtime error: integer divide by zero")
+    n_full = istft_length(nsegs, nfft, noverlap) if nsegs > 1 else nfft
+    n = n_full if n is None else int(n)
+    if n < 0 or n > n_full:
+        raise Panic(_lib.GDSP_ERR_INVALID, "n = %d outside [0, %d]" % (n, n_full))
+    out = np.empty((channels, n), np.float64)
+    if n == 0 or channels == 0:
+        return out
+    no = _lib._I64(0)
+    check(lib().gdsp_istft_batch(_p(X), channels, nsegs, nfft, pad, noverlap, _p(win_seg), n,
+                                 _p(out), n, no), "IstftBatch")
+    return out
+
+
+def Istft(X, o: Optional[PwelchOptions], n: Optional[int] = None):
+    """The inverse of Stft: X[nsegs, Pad / 2 + 1] -> x[n] (IstftBatch of one
+    channel). Istft(Stft(x)[0], o, n=len(x)) is x wherever the window gives a
+    sample weight."""
+    X = np.asarray(X)
+    if X.ndim != 2:
+        raise Panic(_lib.GDSP_ERR_INVALID, "X must be nsegs x (Pad/2+1)")
+    return IstftBatch(X.reshape((1,) + X.shape), o, n)[0]
+
+
 def Spectrogram(x, Fs: float, o: Optional[PwelchOptions]):
     """The spectrogram of one signal (MATLAB spectrogram's ps, scipy.signal.
     spectrogram): SpectrogramBatch of one row. Returns (P[nsegs, lp], freqs,

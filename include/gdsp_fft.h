@@ -118,7 +118,13 @@ enum {
    * materialised form (gathered real rows, the plan's batched transform, a
    * kernel that writes the first lp bins or their powers) also for the lengths
    * the fused per-segment kernel serves. Read when the call is made. */
-  GDSP_ALGO_NO_FUSED_STFT = 1024
+  GDSP_ALGO_NO_FUSED_STFT = 1024,
+  /* gdsp_istft_batch and its device entry on the materialised form (rows
+   * completed to dense complex rows, the plan's batched inverse transform, an
+   * overlap-add kernel with one thread per output sample) also for the shapes
+   * the fused overlap-add kernel serves. Read when the call is made. The bit
+   * 2048 is not used: it stays an unknown bit. */
+  GDSP_ALGO_NO_FUSED_ISTFT = 4096
 };
 /* Unknown bits → GDSP_ERR_INVALID (the selection is left unchanged). */
 int gdsp_set_algorithm(unsigned flags);
@@ -148,6 +154,16 @@ unsigned gdsp_get_algorithm(void);
  *                             segment of both signals (a shared y: all channels)
  *      STFT, spectrogram      every bin of the rows of the segments that hold
  *                             the sample (tests/test_stft_gpu.py)
+ *      ISTFT                  a bad used element of row (c, s): non-finite
+ *                             samples only among [s*stride, s*stride + nfft)
+ *                             of channel c with D > 0; all of those for a bad
+ *                             real part of bin 0 or F/2, which has a weight in
+ *                             every sample (another bin's cosine or sine is
+ *                             exactly 0 at some samples, which the transform
+ *                             may or may not reach); zero-weight terms are
+ *                             not skipped. Rows times 2^k give samples times
+ *                             2^k; every sample is summed over its segments
+ *                             in ascending s (tests/test_istft_gpu.py)
  *      FIR                   outputs [j, j + m) of that row for a bad x[j],
  *                             and possibly more of (j - 2F, j + 2F), F =
  *                             gdsp_fir_block's: a transform carries two blocks
@@ -412,6 +428,51 @@ int gdsp_spectrogram_batch(const double *x, int64_t channels, int64_t n, int64_t
 int gdsp_stft_batch_fused(int64_t channels, int64_t n, int64_t nfft, int64_t pad,
                           int64_t noverlap);
 
+/* The inverse of gdsp_stft_batch by weighted overlap-add (no reference
+ * equivalent; MATLAB istft, scipy.signal.istft: the least-squares inverse of
+ * Griffin and Lim). Options, defaults, F = max(pad, nfft), stride = nfft -
+ * noverlap, lp = pad/2+1 and the window w = win_seg[0 .. nfft) (the first nfft
+ * entries of the window of F, NULL = Hann) are gdsp_stft_batch's; pad >= nfft
+ * after the defaults is required (a row with pad < nfft is a truncated
+ * spectrum and has no inverse). X is channels x nsegs x lp complex128, dense.
+ * For channel c with rows X_s:
+ *   y_s    = the first nfft samples of the F-point inverse real transform of
+ *            X_s (Hermitian completion of the lp bins, 1/F included; the
+ *            imaginary parts of bins 0 and, F even, F/2 are not read)
+ *   num[i] = sum_s w[i - s*stride] y_s[i - s*stride]   over the segments that
+ *   D[i]   = sum_s w[i - s*stride]^2                   cover i, ascending s
+ *   out[c*ldo + i] = num[i] / D[i] where D[i] > 0, exactly 0 where D[i] == 0
+ * for i < n_full = (nsegs-1)*stride + nfft. D == 0 is an exact test, not a
+ * threshold: on rows from gdsp_stft_batch the result is the signal wherever
+ * D > 0, for any window and overlap (no COLA condition). n == 0 means n_full;
+ * *n_out = the samples written per row.
+ * Accuracy: the fused kernel packs rows (2p, 2p+1), by absolute index, into
+ * one inverse transform, balanced by a power of 2 from the binary exponents
+ * of the two rows' maxima and taken out again exactly (gdsp_stft_batch): a
+ * quiet row beside a loud one keeps its digits, a row of zeros contributes
+ * exact zeros, and a pair that holds a NaN or an infinity runs its two rows in
+ * transforms of their own, so a row's samples depend on its pair alone.
+ * Before any device call: a NULL n_out or a needed NULL X or out, negative
+ * counts, nfft < 0, pad < nfft after the defaults, n > n_full, ldo < n with
+ * channels > 1 -> GDSP_ERR_INVALID; a zero stride with nsegs > 1 ->
+ * GDSP_ERR_DIVIDE_BY_ZERO. channels == 0 or nsegs == 0: nothing is written
+ * (*n_out = 0 for nsegs == 0). The device copy of X is held to 2^25 complex
+ * elements: longer inputs run as output ranges that begin at multiples of
+ * 2*stride, each with the rows that reach into it, so no bit depends on the
+ * cut. F a power of 2 from 64 to 2048 with 0 <= noverlap and nfft <= 4*stride
+ * runs one fused kernel (gdsp_istft_batch_fused); every other shape the
+ * materialised form. Runs on the current device. */
+int gdsp_istft_batch(const void *X, int64_t channels, int64_t nsegs, int64_t nfft, int64_t pad,
+                     int64_t noverlap, const double *win_seg, int64_t n, double *out, int64_t ldo,
+                     int64_t *n_out);
+/* 1: a call of gdsp_istft_batch or its device entry of this shape (0 = the
+ * defaults) runs the fused kernel under the current flags; 0: the materialised
+ * form (F < 64, F = 4096 and up, non-powers of 2, pad < nfft, more than 4
+ * segments over a sample, a negative noverlap, GDSP_ALGO_NO_FUSED_ISTFT). Host
+ * arithmetic only (no GPU needed). */
+int gdsp_istft_batch_fused(int64_t channels, int64_t nsegs, int64_t nfft, int64_t pad,
+                           int64_t noverlap);
+
 /* window.Hann — window/window.go:62-76, as a host table generator used by the
  * shim for the default window (L float64 written to out). */
 int gdsp_window_hann(int64_t L, double *out);
@@ -467,10 +528,11 @@ int gdsp_multi_stats(int64_t *batch_calls, int64_t *pwelch_calls, int64_t *rccl_
  * channels-per-launch loops of the fused batched Pwelch and Cpsd, the channel
  * loop of the batched Pwelch where it has no fused kernel, the segment ranges
  * of gdsp_stft_batch / gdsp_spectrogram_batch and the channel and segment runs
- * of their materialised form, the composed FIR's
+ * of their materialised form, the output ranges of gdsp_istft_batch and the
+ * channel and segment runs of its materialised form, the composed FIR's
  * transform chunks, and the 65535-row pieces of gdsp_fft_axis_device /
  * gdsp_fftn_device and of the multi-pass, four-step and chirp-z executors).
- * multi_unit_launches: launches of a Pwelch, batched-Pwelch, Cpsd or STFT kernel
+ * multi_unit_launches: launches of a Pwelch, batched-Pwelch, Cpsd, STFT or ISTFT kernel
  * whose persistent workers each take at least two pairs (or pair groups). A
  * test reads both before and after a call to prove that the call reached the
  * path it was shaped for. Any pointer may be NULL. */
@@ -710,6 +772,28 @@ int gdsp_spectrogram_batch_device(const double *d_x, int64_t ldx, int64_t channe
                                   int64_t nfft, int64_t pad, int64_t noverlap, int64_t seg_begin,
                                   int64_t seg_end, const double *d_win_seg, double norm,
                                   double *d_out, int64_t ld_seg, int64_t ld_chan, void *stream);
+
+/* gdsp_istft_batch on device buffers: samples [out_begin, out_end) of every
+ * channel, out_end <= n_full, into d_out[c*ldo + (i - out_begin)]. d_X holds
+ * rows seg_row0 ... seg_row0 + seg_rows - 1 of every channel: row (c, s) at
+ * element c*ld_chan + (s - seg_row0)*ld_seg, its lp complex128 contiguous. The
+ * rows of every segment that covers a sample of the range must be present,
+ * and for the shapes gdsp_istft_batch_fused serves the partner of each such
+ * row in its pair (2p, 2p+1) too, where nsegs has one: the fused kernel
+ * transforms a pair together and a row's bits depend on its partner. Other
+ * rows are not read. Any range then gives the bits of the whole call; a range
+ * that no segment covers (a negative noverlap leaves gaps) is zeros. A
+ * needed NULL pointer, negative counts, nfft <= 0, pad < nfft, ld_seg < lp,
+ * ld_chan < seg_rows*ld_seg or ldo < out_end - out_begin with channels > 1, a
+ * reversed range, out_end > n_full, seg_row0 + seg_rows > nsegs or a missing
+ * row -> GDSP_ERR_INVALID; a zero stride with nsegs > 1 ->
+ * GDSP_ERR_DIVIDE_BY_ZERO; all before any device call. channels == 0, nsegs
+ * == 0 or an empty range: nothing is written, GDSP_OK. */
+int gdsp_istft_batch_device(const void *d_X, int64_t ld_seg, int64_t ld_chan, int64_t channels,
+                            int64_t nsegs, int64_t seg_row0, int64_t seg_rows, int64_t nfft,
+                            int64_t pad, int64_t noverlap, const double *d_win_seg,
+                            int64_t out_begin, int64_t out_end, double *d_out, int64_t ldo,
+                            void *stream);
 
 /* gdsp_wav_read_floats_device for a multi-channel data chunk, into planar
  * float64 rows: d_out[c*ld_out + i] = the widened float32 of sample c of
