@@ -58,6 +58,11 @@ SIGNATURES = {
     "gdsp_fir_batch": (_I, [_P, _I64, _P, _I64, _I64, _I64, _I64, _I, _I64, _P, _I64]),
     "gdsp_fir_batch_device": (_I, [_P, _I64, _P, _I64, _I64, _I64, _I64, _I, _I64, _P, _I64, _P,
                                    _P]),
+    "gdsp_upfirdn_length": (_I64, [_I64, _I64, _I64, _I64]),
+    "gdsp_upfirdn_fused": (_I, [_I64, _I64, _I64]),
+    "gdsp_upfirdn_batch": (_I, [_P, _I64, _P, _I64, _I64, _I64, _I64, _I64, _I64, _I64, _P, _I64]),
+    "gdsp_upfirdn_batch_device": (_I, [_P, _I64, _P, _I64, _I64, _I64, _I64, _I64, _I64, _I64, _P,
+                                       _I64, _P, _P]),
     "gdsp_fft_batch": (_I, [_P, _P, _I64, _I64, _I]),
     "gdsp_fft_real_batch": (_I, [_P, _P, _I64, _I64]),
     "gdsp_fft2": (_I, [_P, _P, _I64, _I64, _I]),

@@ -81,7 +81,8 @@ constexpr unsigned kAlgoAll = GDSP_ALGO_GENERIC_MIXED | GDSP_ALGO_NO_CHIRPZ_PART
                               GDSP_ALGO_NO_RADER | GDSP_ALGO_NO_RACE |
                               GDSP_ALGO_NO_FUSED_CONVOLVE | GDSP_ALGO_NO_FUSED_PWELCH_BATCH |
                               GDSP_ALGO_NO_FUSED_CPSD | GDSP_ALGO_NO_FUSED_FIR |
-                              GDSP_ALGO_NO_FUSED_STFT | GDSP_ALGO_NO_FUSED_ISTFT;
+                              GDSP_ALGO_NO_FUSED_STFT | GDSP_ALGO_NO_FUSED_ISTFT |
+                              GDSP_ALGO_NO_FUSED_UPFIRDN;
 
 // Scratch device memory: a grow-only buffer per (device, stream, use-site
 // slot), allocated with hipMalloc. Reuse is ordered by the stream itself: a
@@ -1209,6 +1210,157 @@ int gdsp_fir_batch(const double *x, int64_t ldx, const double *h, int64_t h_rows
   // every sample left the caller's memory before the first result lands in
   // it, so out may alias x
   return unstage_rows(out, po, channels, out_len, ldo, s);
+}
+
+// ---- polyphase resampling of real rows (upfirdn.hip) --------------------------
+static constexpr int64_t kUpfirdnMaxRate = 65536, kUpfirdnMaxTaps = (int64_t)1 << 24;
+// outputs of one chunk of the host entry (all rows together)
+static constexpr int64_t UPFIRDN_CHUNK_ELEMS = (int64_t)1 << 25;
+
+// (n - 1) up + m, or -1 where int64 does not hold it (n, m, up >= 1)
+static int64_t upfirdn_full_len(int64_t n, int64_t m, int64_t up) {
+  int64_t v = 0;
+  if (__builtin_mul_overflow(n - 1, up, &v) || __builtin_add_overflow(v, m, &v)) return -1;
+  return v;
+}
+
+static bool upfirdn_supported(int64_t n, int64_t m, int64_t up, int64_t down) {
+  return up <= kUpfirdnMaxRate && down <= kUpfirdnMaxRate && m <= kUpfirdnMaxTaps &&
+         upfirdn_full_len(n, m, up) >= 0;
+}
+
+int64_t gdsp_upfirdn_length(int64_t n, int64_t m, int64_t up, int64_t down) {
+  if (n < 0 || m < 0 || up < 1 || down < 1) return -1;
+  if (n == 0 || m == 0) return 0;
+  if (!upfirdn_supported(n, m, up, down)) return -1;
+  return (upfirdn_full_len(n, m, up) - 1) / down + 1;
+}
+
+int gdsp_upfirdn_fused(int64_t m, int64_t up, int64_t down) {
+  return !(g_algo.load() & GDSP_ALGO_NO_FUSED_UPFIRDN) && gdsp::upfirdn_geometry(m, up, down).fits;
+}
+
+// Argument checks shared by the host and device entries, in the order of the
+// header's table, up to the NULL pointers; *done: nothing to do; *out_end: the
+// range's end with -1 resolved. No device call is made.
+static int upfirdn_check(const void *x, int64_t ldx, const void *h, int64_t m, int64_t up,
+                         int64_t down, int64_t channels, int64_t n, int64_t out_begin,
+                         int64_t *out_end, const void *out, int64_t ldo, bool *done) {
+  *done = false;
+  if (m < 0 || n < 0 || channels < 0) return fail(GDSP_ERR_INVALID, "negative size");
+  if (up < 1 || down < 1) return fail(GDSP_ERR_INVALID, "up and down must be at least 1");
+  // L, saturated where int64 does not hold (n - 1) up + m (refused below)
+  int64_t L = 0;
+  if (n > 0 && m > 0) {
+    const int64_t full = upfirdn_full_len(n, m, up);
+    L = full < 0 ? INT64_MAX : (full - 1) / down + 1;
+  }
+  if (*out_end == -1) *out_end = L;
+  if (out_begin < 0 || out_begin > *out_end || *out_end > L)
+    return fail(GDSP_ERR_INVALID, "output range not within [0, L]");
+  if (channels > 1 && (ldx < n || ldo < *out_end - out_begin))
+    return fail(GDSP_ERR_INVALID, "row stride below the row length");
+  if (channels == 0) {
+    *done = true;
+    return GDSP_OK;
+  }
+  if (n == 0 || m == 0) return fail(GDSP_ERR_EMPTY, "empty input array");
+  if (!upfirdn_supported(n, m, up, down))
+    return fail(GDSP_ERR_UNSUPPORTED, "up or down above 65536, more than 2^24 taps, or a length "
+                                      "beyond int64");
+  if (!x || !h || !out) return fail(GDSP_ERR_INVALID, "NULL pointer");
+  return GDSP_OK;
+}
+
+// Outputs [out_begin, out_end) of every row; the rows at d_x hold samples
+// [x_lo, x_hi) of the signal. work: up ceil(m / up) doubles.
+static int upfirdn_rows(const double *d_x, int64_t ldx, int64_t x_lo, int64_t x_hi,
+                        const double *d_h, int64_t m, int64_t up, int64_t down, int64_t channels,
+                        int64_t out_begin, int64_t out_end, double *d_out, int64_t ldo,
+                        double *work, hipStream_t s) {
+  HIPCHK(gdsp::launch_upfirdn_taps(d_h, m, up, work, s));
+  const gdsp::UpfirdnGeo g = gdsp::upfirdn_geometry(m, up, down);
+  if (g.fits && !(g_algo.load() & GDSP_ALGO_NO_FUSED_UPFIRDN)) {
+    HIPCHK(gdsp::launch_upfirdn_poly(g, d_x, ldx, x_lo, x_hi, work, up, down, channels, out_begin,
+                                     out_end, d_out, ldo, s));
+  } else {
+    HIPCHK(gdsp::launch_upfirdn_plain(d_x, ldx, x_lo, x_hi, work, m, up, down, channels,
+                                      out_begin, out_end, d_out, ldo, s));
+  }
+  return GDSP_OK;
+}
+
+static size_t upfirdn_work_bytes(int64_t m, int64_t up) {
+  return (size_t)(up * ((m + up - 1) / up)) * sizeof(double);
+}
+
+int gdsp_upfirdn_batch_device(const void *d_x, int64_t ldx, const void *d_h, int64_t m,
+                              int64_t up, int64_t down, int64_t channels, int64_t n,
+                              int64_t out_begin, int64_t out_end, void *d_out, int64_t ldo,
+                              void *d_work, void *stream) {
+  bool done = false;
+  STCHK(upfirdn_check(d_x, ldx, d_h, m, up, down, channels, n, out_begin, &out_end, d_out, ldo,
+                      &done));
+  if (done) return GDSP_OK;
+  const int64_t cnt = out_end - out_begin;
+  // a tile's halo is read while another workgroup stores: no overlap at all
+  const uintptr_t xa = (uintptr_t)d_x, oa = (uintptr_t)d_out;
+  const uintptr_t xe = xa + ((uintptr_t)(channels - 1) * (uintptr_t)ldx + (uintptr_t)n) * 8;
+  const uintptr_t oe = oa + ((uintptr_t)(channels - 1) * (uintptr_t)ldo + (uintptr_t)cnt) * 8;
+  if (xa < oe && oa < xe) return fail(GDSP_ERR_INVALID, "d_out overlaps d_x");
+  if (cnt == 0) return GDSP_OK;
+  int dev = 0;
+  STCHK(current_device(&dev));
+  hipStream_t s = (hipStream_t)stream;
+  DevBuf w;
+  double *work = (double *)d_work;
+  if (!work) {
+    STCHK(w.alloc(upfirdn_work_bytes(m, up), s, SLOT_UF));
+    work = (double *)w.p;
+  }
+  return upfirdn_rows((const double *)d_x, channels > 1 ? ldx : n, 0, n, (const double *)d_h, m,
+                      up, down, channels, out_begin, out_end, (double *)d_out,
+                      channels > 1 ? ldo : cnt, work, s);
+}
+
+int gdsp_upfirdn_batch(const double *x, int64_t ldx, const double *h, int64_t m, int64_t up,
+                       int64_t down, int64_t channels, int64_t n, int64_t out_begin,
+                       int64_t out_end, double *out, int64_t ldo) {
+  bool done = false;
+  STCHK(upfirdn_check(x, ldx, h, m, up, down, channels, n, out_begin, &out_end, out, ldo, &done));
+  if (done || out_end == out_begin) return GDSP_OK;
+  int dev = 0;
+  STCHK(current_device(&dev));
+  hipStream_t s = thread_stream(dev);
+  if (!s) return fail(GDSP_ERR_HIP, "stream creation failed");
+  const int64_t T = (m + up - 1) / up;
+  int64_t rng = UPFIRDN_CHUNK_ELEMS / channels;  // outputs of a row per chunk
+  if (rng < 1) rng = 1;
+  if (channels == 1) ldx = n, ldo = out_end - out_begin;
+  DevBuf dx, dh, dout, dw;
+  STCHK(dh.alloc((size_t)m * sizeof(double), s, SLOT_UF_H));
+  STCHK(dw.alloc(upfirdn_work_bytes(m, up), s, SLOT_UF));
+  for (int64_t jb = out_begin; jb < out_end; jb += rng) {
+    later_chunk(jb - out_begin);
+    const int64_t je = out_end - jb < rng ? out_end : jb + rng, cnt = je - jb;
+    // the samples the chunk reads: [i0(jb) - (T - 1), i0(je - 1)] within the row
+    int64_t ib = jb * down / up - (T - 1), ie = (je - 1) * down / up + 1;
+    if (ib < 0) ib = 0;
+    if (ie > n) ie = n;
+    const int64_t len = ie - ib;
+    STCHK(dx.alloc((size_t)channels * (size_t)len * sizeof(double), s, SLOT_IN));
+    STCHK(dout.alloc((size_t)channels * (size_t)cnt * sizeof(double), s, SLOT_UF_OUT));
+    double *px = (double *)dx.p, *po = (double *)dout.p;
+    STCHK(run_queued(s, [&]() -> int {
+      STCHK(stage_rows(px, x + ib, channels, len, ldx, len, s));
+      if (jb == out_begin) STCHK(copy_h2d(dh.p, h, (size_t)m * sizeof(double), s));
+      return upfirdn_rows(px, len, ib, ie, (const double *)dh.p, m, up, down, channels, jb, je, po,
+                          cnt, (double *)dw.p, s);
+    }));
+    // returns after the stream drained: the next chunk may reuse the buffers
+    STCHK(unstage_rows(out + (jb - out_begin), po, channels, cnt, ldo, s));
+  }
+  return GDSP_OK;
 }
 
 int gdsp_fft2_device(const void *d_in, void *d_out, int64_t rows, int64_t cols, int inverse,

@@ -359,6 +359,32 @@ hipError_t launch_fir_gather(const double *x, int64_t ldx, int64_t g0, int64_t c
                              int64_t n, int64_t m, int64_t F, cd *buf, hipStream_t s);
 hipError_t launch_fir_scatter(const cd *buf, int64_t g0, int64_t cnt, int64_t tpr, int64_t out_len,
                               int64_t m, int64_t F, double *out, int64_t ldo, hipStream_t s);
+// Polyphase resampling of real rows (upfirdn.hip): out[c ldo + j - out_begin] =
+// sum_{t<T} hp[p T + t] x[c ldx + i0 - t - x_lo], p = (j down) mod up, i0 =
+// (j down) div up, T = ceil(m / up), for j in [out_begin, out_end); the rows
+// hold samples [x_lo, x_hi) of the signal (the rest counts as 0). hp: the
+// phase-major taps launch_upfirdn_taps writes (up T doubles). The fused form
+// runs on the geometry upfirdn_geometry admits (fits == false: none); both
+// launchers cut a grid past 2^31 - 1 workgroups into runs of channels.
+struct UpfirdnGeo {
+  bool fits;     // the fused kernel serves the shape
+  int T, Tp;     // taps per phase; the row length of the table in LDS
+  int Q, E;      // a thread's slots are Q apart (a multiple of the phase period); outputs each
+  bool pad;      // the tile in LDS with one padding double every 32
+  int QD;        // Q down / up: the samples between a slot's outputs
+  int span;      // samples of a tile: ((Q E - 1) down + up - 1) div up + T
+  int lds_doubles;
+};
+UpfirdnGeo upfirdn_geometry(int64_t m, int64_t up, int64_t down);
+hipError_t launch_upfirdn_taps(const double *h, int64_t m, int64_t up, double *hp, hipStream_t s);
+hipError_t launch_upfirdn_poly(const UpfirdnGeo &g, const double *x, int64_t ldx, int64_t x_lo,
+                               int64_t x_hi, const double *hp, int64_t up, int64_t down,
+                               int64_t channels, int64_t out_begin, int64_t out_end, double *out,
+                               int64_t ldo, hipStream_t s);
+hipError_t launch_upfirdn_plain(const double *x, int64_t ldx, int64_t x_lo, int64_t x_hi,
+                                const double *hp, int64_t m, int64_t up, int64_t down,
+                                int64_t channels, int64_t out_begin, int64_t out_end, double *out,
+                                int64_t ldo, hipStream_t s);
 // wav.ReadFloats conversion (wav.hip): audio_format 1 (bits 8 / 16) or 3
 hipError_t launch_wav_decode(const void *in, int64_t count, int audio_format, int bits,
                              void *out, bool f64, hipStream_t s);

@@ -158,6 +158,83 @@ def fir_batch(x, h, out=None, full: bool = False, block: int = 0, work=None, str
     return out
 
 
+def upfirdn_batch(x, h, up: int = 1, down: int = 1, out=None, out_begin: int = 0, out_end=None,
+                  work=None, stream=None):
+    """fft.UpfirdnBatch on float64 CUDA tensors: every row of x (channels, n;
+    unit inner stride, any row stride) zero-stuffed by up, filtered with the
+    taps h (m,) and decimated by down (scipy.signal.upfirdn(h, x, up, down)).
+    Outputs [out_begin, out_end) of every row (out_end None: to the end,
+    fft.upfirdn_length) go into out (channels, out_end - out_begin; unit inner
+    stride, any row stride), which must not overlap x. work: scratch (float64)
+    of up * ceil(m / up) elements for the phase-major taps; with it the call
+    neither allocates nor synchronises (gdsp_upfirdn_batch_device)."""
+    torch = _torch()
+    assert x.is_cuda and x.dtype == torch.float64 and x.dim() == 2
+    assert h.is_cuda and h.dtype == torch.float64 and h.device == x.device
+    assert h.dim() == 1 and h.is_contiguous()
+    channels, n = x.shape
+    m = h.shape[0]
+    up, down = int(up), int(down)
+    L = int(lib().gdsp_upfirdn_length(n, m, up, down))
+    end = L if out_end is None else int(out_end)
+    cnt = max(end - int(out_begin), 0)
+    if out is None:
+        out = torch.empty((channels, cnt), dtype=torch.float64, device=x.device)
+    assert out.is_cuda and out.dtype == torch.float64 and out.device == x.device
+    assert tuple(out.shape) == (channels, cnt)
+    assert n == 0 or x.stride(1) == 1, "rows must have unit inner stride"
+    assert cnt == 0 or out.stride(1) == 1, "rows must have unit inner stride"
+    ldx = x.stride(0) if channels > 1 else n
+    ldo = out.stride(0) if channels > 1 else cnt
+    if work is not None:
+        assert work.is_cuda and work.dtype == torch.float64 and work.is_contiguous()
+        assert work.numel() >= up * -(-m // up)
+    with torch.cuda.device(x.device):
+        wp = _ptr(work) if work is not None else ctypes.c_void_p()
+        check(lib().gdsp_upfirdn_batch_device(_ptr(x), ldx, _ptr(h), m, up, down, channels, n,
+                                              int(out_begin), end, _ptr(out), ldo, wp,
+                                              _stream_ptr(stream, x.device)),
+              "upfirdn_batch_device")
+    return out
+
+
+def resample_poly_batch(x, up: int, down: int, taps=None, out=None, stream=None):
+    """fft.ResamplePolyBatch on a float64 CUDA tensor (channels, n):
+    scipy.signal.resample_poly(x, up, down, axis=1) with its default zero
+    padding, ceil(n up / down) samples per row. taps: the low-pass as it is, a
+    1-D array or tensor (None: fft.resample_taps). One upfirdn_batch call on
+    the padded taps whose range starts after the dropped outputs; up == down
+    copies."""
+    torch = _torch()
+    import numpy as np
+
+    from . import fft
+    assert x.is_cuda and x.dtype == torch.float64 and x.dim() == 2
+    u, d = fft._rate_pair(up, down)
+    channels, n = x.shape
+    if taps is None:
+        h = fft.resample_taps(u, d)
+    elif torch.is_tensor(taps):
+        h = taps.detach().cpu().numpy()
+    else:
+        h = taps
+    if np.iscomplexobj(h):
+        raise TypeError("resample_poly_batch: complex taps are not supported")
+    h = np.asarray(h, dtype=np.float64).reshape(-1)
+    pl = fft.resample_plan(n, u, d, h.size)
+    if out is None:
+        out = torch.empty((channels, pl["n_out"]), dtype=torch.float64, device=x.device)
+    assert tuple(out.shape) == (channels, pl["n_out"])
+    if u == d:
+        out.copy_(x)
+        return out
+    if channels == 0 or n == 0:
+        return out
+    hh = np.concatenate([np.zeros(pl["pre"]), h, np.zeros(pl["post"])])
+    return upfirdn_batch(x, torch.from_numpy(hh).to(x.device), u, d, out=out,
+                         out_begin=pl["rem"], out_end=pl["rem"] + pl["n_out"], stream=stream)
+
+
 def fft_real_batch(x, out=None, inverse: bool = False, stream=None, chirpz: bool = False):
     """fft.FFTReal / IFFTReal of the rows of a (batch, n) float64 CUDA tensor
     into a complex128 tensor (gdsp_fft_real_batch_device: the kernels read the

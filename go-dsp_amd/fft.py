@@ -157,6 +157,124 @@ def ConvolveLinear(x, h) -> np.ndarray:
     return FIRFilterBatch(np.asarray(x, dtype=np.float64).reshape(1, -1), h, full=True)[0]
 
 
+def upfirdn_length(n: int, m: int, up: int = 1, down: int = 1) -> int:
+    """L = ((n - 1) up + m - 1) div down + 1, the outputs per row of UpfirdnBatch;
+    0 for n = 0 or m = 0, -1 where the call would be refused
+    (gdsp_upfirdn_length; host arithmetic)."""
+    return int(lib().gdsp_upfirdn_length(int(n), int(m), int(up), int(down)))
+
+
+def upfirdn_fused(m: int, up: int = 1, down: int = 1) -> bool:
+    """Whether UpfirdnBatch runs m taps at up/down on the fused polyphase
+    kernel under the current algorithm flags (gdsp_upfirdn_fused; host
+    arithmetic)."""
+    return bool(lib().gdsp_upfirdn_fused(int(m), int(up), int(down)))
+
+
+def UpfirdnBatch(rows, h, up: int = 1, down: int = 1, out_begin: int = 0,
+                 out_end: int | None = None) -> np.ndarray:
+    """Additive polyphase resampling of every row of the real (channels, n)
+    array (or list of rows) with the real taps h (one set for all rows):
+    scipy.signal.upfirdn(h, rows, up, down) — zero-stuff by up, filter, keep
+    every down-th sample: out[c, j] = sum_i h[j down - i up] rows[c, i], j in
+    [0, upfirdn_length(n, m, up, down)). out_begin, out_end: only that range
+    of the outputs (out_end None: to the end)."""
+    x = _real_rows(rows, "UpfirdnBatch")
+    if np.iscomplexobj(h):
+        raise TypeError("UpfirdnBatch: complex taps are not supported")
+    h = np.asarray(h, dtype=np.float64)
+    if h.ndim != 1:
+        raise Panic(_lib.GDSP_ERR_UNEQUAL, "arrays not of equal size")
+    h = np.ascontiguousarray(h)
+    channels, n = x.shape
+    m = h.size
+    L = upfirdn_length(n, m, up, down)
+    end = L if out_end is None else int(out_end)
+    out = np.empty((channels, max(end - int(out_begin), 0)), np.float64)
+    check(lib().gdsp_upfirdn_batch(_p(x), n, _p(h), m, int(up), int(down), channels, n,
+                                   int(out_begin), end, _p(out), out.shape[1]), "UpfirdnBatch")
+    return out
+
+
+def Upfirdn(x, h, up: int = 1, down: int = 1) -> np.ndarray:
+    """scipy.signal.upfirdn(h, x, up, down) of the real signal x (UpfirdnBatch
+    of one row)."""
+    if np.iscomplexobj(x):
+        raise TypeError("Upfirdn: complex input is not supported")
+    return UpfirdnBatch(np.asarray(x, dtype=np.float64).reshape(1, -1), h, up, down)[0]
+
+
+def _rate_pair(up: int, down: int) -> tuple[int, int]:
+    import math
+    up, down = int(up), int(down)
+    if up < 1 or down < 1:
+        raise _lib.GDSPError(_lib.GDSP_ERR_INVALID, "up and down must be at least 1")
+    g = math.gcd(up, down)
+    return up // g, down // g
+
+
+def resample_taps(up: int, down: int) -> np.ndarray:
+    """The anti-alias low-pass ResamplePoly uses by default, scipy's
+    firwin(2 half + 1, 1 / R, window=('kaiser', 5.0)) * up with R = max(up,
+    down) after the gcd reduction and half = 10 R: h[k] = (1 / R) sinc((k -
+    half) / R) kaiser(2 half + 1, 5.0)[k], divided by its sum, times up."""
+    up, down = _rate_pair(up, down)
+    R = max(up, down)
+    half = 10 * R
+    k = np.arange(2 * half + 1) - half
+    h = (1.0 / R) * np.sinc(k / R) * np.kaiser(2 * half + 1, 5.0)
+    h /= h.sum()
+    return h * up
+
+
+def resample_plan(n: int, up: int, down: int, m: int | None = None) -> dict:
+    """The arithmetic of ResamplePoly (scipy.signal.resample_poly's) for rows
+    of n samples and m taps (None: resample_taps'): the reduced up and down,
+    half = (m - 1) div 2, pre zeros in front of the taps and post behind them,
+    rem outputs dropped in front and n_out = ceil(n up / down) kept."""
+    up, down = _rate_pair(up, down)
+    if m is None:
+        m = 20 * max(up, down) + 1
+    half = (int(m) - 1) // 2
+    n_out = -(-int(n) * up // down)
+    pre = down - half % down
+    rem = (half + pre) // down
+    post = 0
+    while n > 0 and ((n - 1) * up + m + pre + post - 1) // down + 1 < n_out + rem:
+        post += 1
+    return {"up": up, "down": down, "half": half, "pre": pre, "post": post, "rem": rem,
+            "n_out": n_out}
+
+
+def ResamplePolyBatch(rows, up: int, down: int, taps=None) -> np.ndarray:
+    """scipy.signal.resample_poly(rows, up, down, axis=1) with its default
+    zero padding: every row of the real (channels, n) array at up / down
+    times its rate, ceil(n up / down) samples, the filter's delay removed.
+    taps: the low-pass to use as it is (None: resample_taps(up, down)); its
+    centre is tap (len - 1) div 2. One UpfirdnBatch call on the padded taps
+    whose range starts after the dropped outputs; up == down returns a copy."""
+    x = _real_rows(rows, "ResamplePolyBatch")
+    if taps is not None and np.iscomplexobj(taps):
+        raise TypeError("ResamplePolyBatch: complex taps are not supported")
+    u, d = _rate_pair(up, down)
+    if u == d:
+        return x.copy()
+    h = resample_taps(u, d) if taps is None else np.asarray(taps, dtype=np.float64).reshape(-1)
+    pl = resample_plan(x.shape[1], u, d, h.size)
+    if x.shape[0] == 0 or x.shape[1] == 0:
+        return np.empty((x.shape[0], pl["n_out"]), np.float64)
+    hh = np.concatenate([np.zeros(pl["pre"]), h, np.zeros(pl["post"])])
+    return UpfirdnBatch(x, hh, u, d, pl["rem"], pl["rem"] + pl["n_out"])
+
+
+def ResamplePoly(x, up: int, down: int, taps=None) -> np.ndarray:
+    """scipy.signal.resample_poly(x, up, down) of the real signal x
+    (ResamplePolyBatch of one row)."""
+    if np.iscomplexobj(x):
+        raise TypeError("ResamplePoly: complex input is not supported")
+    return ResamplePolyBatch(np.asarray(x, dtype=np.float64).reshape(1, -1), up, down, taps)[0]
+
+
 def FFTBatch(x, inverse: bool = False) -> np.ndarray:
     """Additive batched entry point: FFT (or IFFT) of every row
     of a (batch, n) complex array, in one GPU launch."""
@@ -301,6 +419,7 @@ ALGO_NO_FUSED_CPSD = 256
 ALGO_NO_FUSED_FIR = _lib.GDSP_ALGO_NO_FUSED_FIR
 ALGO_NO_FUSED_STFT = 1024
 ALGO_NO_FUSED_ISTFT = 4096  # 2048 is not a flag
+ALGO_NO_FUSED_UPFIRDN = 8192
 
 
 def SetAlgorithm(flags: int = ALGO_DEFAULT) -> None:

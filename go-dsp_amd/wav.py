@@ -308,6 +308,27 @@ def FilterChannels(w: Wav, frames: int, h, full: bool = False):
     return out.cpu().numpy()
 
 
+def ResampleChannels(w: Wav, frames: int, rate: int):
+    """Every channel of a multi-channel file at the sample rate `rate`: the
+    next `frames` frames of w, decoded planar on the GPU as for FilterChannels
+    and run through device.resample_poly_batch with up / down = rate /
+    w.SampleRate reduced. Returns a (NumChannels, ceil(frames up / down))
+    numpy array; row c equals fft.ResamplePolyBatch of channel c's decoded
+    samples."""
+    import torch
+
+    from . import device, fft
+    up, down = fft._rate_pair(int(rate), int(w.SampleRate))
+    C = int(w.NumChannels)
+    raw, _ = w._read_raw(frames * C)
+    if frames == 0:
+        return np.zeros((C, 0))
+    dev = torch.device("cuda", torch.cuda.current_device())
+    rd = torch.frombuffer(bytearray(raw), dtype=torch.uint8).to(dev)
+    x = device_floats_planar(rd, frames, C, w.AudioFormat, w.BitsPerSample)
+    return device.resample_poly_batch(x, up, down).cpu().numpy()
+
+
 def Pwelch(w: Wav, n: int, o, Fs: float = 0.0):
     """The feeder end to end: the next n samples of w, decoded on the GPU
     into float64 and run through the device Pwelch (no host float pass);

@@ -124,7 +124,11 @@ enum {
    * overlap-add kernel with one thread per output sample) also for the shapes
    * the fused overlap-add kernel serves. Read when the call is made. The bit
    * 2048 is not used: it stays an unknown bit. */
-  GDSP_ALGO_NO_FUSED_ISTFT = 4096
+  GDSP_ALGO_NO_FUSED_ISTFT = 4096,
+  /* gdsp_upfirdn_batch / gdsp_upfirdn_batch_device on the plain form (one
+   * thread per output, taps and samples from global memory) also for the
+   * shapes the fused polyphase kernel serves. Read when the call is made. */
+  GDSP_ALGO_NO_FUSED_UPFIRDN = 8192
 };
 /* Unknown bits → GDSP_ERR_INVALID (the selection is left unchanged). */
 int gdsp_set_algorithm(unsigned flags);
@@ -169,7 +173,18 @@ unsigned gdsp_get_algorithm(void);
  *                             gdsp_fir_block's: a transform carries two blocks
  *                             of F - m + 1 outputs and a sample is read by at
  *                             most two transforms. scipy.signal.lfilter would
- *                             confine it to [j, j + m). */
+ *                             confine it to [j, j + m).
+ *      resampling            a bad x[c, i] (gdsp_upfirdn_batch and its device
+ *                             entry): every output j of row c with 0 <= j*down
+ *                             - i*up < m, none outside 0 <= j*down - i*up <
+ *                             T*up, T = ceil(m / up) (the taps are padded with
+ *                             zeros to T per phase, and zero-weight terms are
+ *                             not skipped); x times 2^a and h times 2^b give
+ *                             the outputs times 2^(a+b); a phase without a tap
+ *                             gives +0.0; every output is summed in ascending t
+ *                             with one fused multiply-add per term, so its bits
+ *                             do not depend on the range, chunk, tile or form
+ *                             that computes it (tests/test_resample_gpu.py) */
 
 /* ---- fft package: host pointers, synchronous ----------------------------- */
 
@@ -240,6 +255,42 @@ int gdsp_fir_batch(const double *x, int64_t ldx, const double *h, int64_t h_rows
  * (256 <= F <= 16384, m <= F/2) under the current flags (a call whose grid
  * would pass 2^31 - 1 workgroups still runs composed). */
 int64_t gdsp_fir_block(int64_t m, int64_t block, int *fused);
+
+/* Additive polyphase resampling of real rows (no reference equivalent;
+ * scipy.signal.upfirdn(h, x, up, down): zero-stuff by up, filter, keep every
+ * down-th sample): for `channels` rows of n float64, row c at x + c*ldx, m
+ * real taps h (one set for all rows) and integers up, down >= 1,
+ *   out[c, j] = sum over i of h[j*down - i*up] * x[c, i],
+ *               0 <= j*down - i*up < m, 0 <= i < n,
+ *   j in [0, L), L = gdsp_upfirdn_length(n, m, up, down)
+ *              = ((n - 1)*up + m - 1) div down + 1,
+ * computed in polyphase form: with p = (j*down) mod up, i0 = (j*down) div up,
+ * T = ceil(m / up): out[c, j] = sum over t < T of h[p + t*up] * x[c, i0 - t],
+ * taps at index >= m and samples outside the row counting as 0, summed in
+ * ascending t. Outputs [out_begin, out_end) of every row are written to out +
+ * c*ldo (out_end == -1: L). Strides in doubles. Longer jobs are cut into
+ * ranges of outputs: the device buffers hold at most 2^25 doubles of output
+ * per chunk (UPFIRDN_CHUNK_ELEMS) and the input span that chunk reads.
+ * In this order, before any device call: a negative size, up < 1 or down < 1,
+ * a range not within 0 <= out_begin <= out_end <= L, or, with channels > 1,
+ * ldx < n or ldo < out_end - out_begin -> GDSP_ERR_INVALID; channels == 0 ->
+ * GDSP_OK, nothing done; n == 0 or m == 0 -> GDSP_ERR_EMPTY; up or down above
+ * 65536, m above 2^24, or (n - 1)*up + m not representable in int64 ->
+ * GDSP_ERR_UNSUPPORTED; a NULL pointer -> GDSP_ERR_INVALID; an empty range ->
+ * GDSP_OK. Runs on the current device. */
+int gdsp_upfirdn_batch(const double *x, int64_t ldx, const double *h, int64_t m, int64_t up,
+                       int64_t down, int64_t channels, int64_t n, int64_t out_begin,
+                       int64_t out_end, double *out, int64_t ldo);
+/* L of gdsp_upfirdn_batch: 0 for n == 0 or m == 0, -1 where the call would be
+ * refused for its sizes (GDSP_ERR_INVALID or GDSP_ERR_UNSUPPORTED above). Host
+ * arithmetic only. */
+int64_t gdsp_upfirdn_length(int64_t n, int64_t m, int64_t up, int64_t down);
+/* 1 where the fused polyphase kernel serves m taps at up/down under the
+ * current flags (the phase table of up * ceil(m / up) doubles and the samples
+ * of the smallest tile fit 64 KiB of LDS), 0 where the plain form runs (also
+ * for sizes the call refuses, and under GDSP_ALGO_NO_FUSED_UPFIRDN). Host
+ * arithmetic on committed constants, no GPU needed. */
+int gdsp_upfirdn_fused(int64_t m, int64_t up, int64_t down);
 
 /* Additive batched entry point (no reference equivalent): the
  * same transform as fft.FFT / fft.IFFT applied to `batch` contiguous rows of n
@@ -530,8 +581,9 @@ int gdsp_multi_stats(int64_t *batch_calls, int64_t *pwelch_calls, int64_t *rccl_
  * of gdsp_stft_batch / gdsp_spectrogram_batch and the channel and segment runs
  * of their materialised form, the output ranges of gdsp_istft_batch and the
  * channel and segment runs of its materialised form, the composed FIR's
- * transform chunks, and the 65535-row pieces of gdsp_fft_axis_device /
- * gdsp_fftn_device and of the multi-pass, four-step and chirp-z executors).
+ * transform chunks, the output ranges of gdsp_upfirdn_batch, and the
+ * 65535-row pieces of gdsp_fft_axis_device / gdsp_fftn_device and of the
+ * multi-pass, four-step and chirp-z executors).
  * multi_unit_launches: launches of a Pwelch, batched-Pwelch, Cpsd, STFT or ISTFT kernel
  * whose persistent workers each take at least two pairs (or pair groups). A
  * test reads both before and after a call to prove that the call reached the
@@ -651,6 +703,20 @@ int gdsp_convolve_fused(const gdsp_plan *plan);
 int gdsp_fir_batch_device(const void *d_x, int64_t ldx, const void *d_h, int64_t h_rows,
                           int64_t m, int64_t channels, int64_t n, int full, int64_t block,
                           void *d_out, int64_t ldo, void *d_work, void *stream);
+
+/* gdsp_upfirdn_batch on device buffers (no reference equivalent),
+ * stream-ordered: d_x rows of n float64 at stride ldx, d_h m float64, d_out
+ * rows of out_end - out_begin float64 at stride ldo (output out_begin of row
+ * c at d_out + c*ldo). The address ranges of d_x and d_out must not overlap
+ * (a tile reads a halo that another workgroup's outputs would overwrite):
+ * GDSP_ERR_INVALID. d_work: scratch of up * ceil(m / up) doubles for the
+ * phase-major taps (may be NULL: the library's workspace pool); with d_work
+ * given the call neither allocates nor synchronises. Status codes as
+ * gdsp_upfirdn_batch, decided before any device call. */
+int gdsp_upfirdn_batch_device(const void *d_x, int64_t ldx, const void *d_h, int64_t m,
+                              int64_t up, int64_t down, int64_t channels, int64_t n,
+                              int64_t out_begin, int64_t out_end, void *d_out, int64_t ldo,
+                              void *d_work, void *stream);
 
 /* FFT2/IFFT2 on a device rows×cols complex128 matrix. d_work: scratch of
  * rows*cols complex128 (may be NULL: the library allocates stream-ordered). */
