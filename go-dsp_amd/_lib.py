@@ -32,6 +32,11 @@ GDSP_ERR_UNSUPPORTED = 9
 # gdsp_set_algorithm: FIR filtering on the composed form (fft.ALGO_NO_FUSED_FIR)
 GDSP_ALGO_NO_FUSED_FIR = 512
 
+# the output of gdsp_hilbert_batch
+GDSP_HILBERT_ANALYTIC = 0
+GDSP_HILBERT_QUADRATURE = 1
+GDSP_HILBERT_ENVELOPE = 2
+
 _P = ctypes.c_void_p
 _I64 = ctypes.c_int64
 _I = ctypes.c_int
@@ -63,6 +68,9 @@ SIGNATURES = {
     "gdsp_upfirdn_batch": (_I, [_P, _I64, _P, _I64, _I64, _I64, _I64, _I64, _I64, _I64, _P, _I64]),
     "gdsp_upfirdn_batch_device": (_I, [_P, _I64, _P, _I64, _I64, _I64, _I64, _I64, _I64, _I64, _P,
                                        _I64, _P, _P]),
+    "gdsp_hilbert_batch": (_I, [_P, _I64, _I64, _I64, _I64, _I, _P, _I64]),
+    "gdsp_hilbert_batch_device": (_I, [_P, _I64, _I64, _I64, _I64, _I, _P, _I64, _P, _P]),
+    "gdsp_hilbert_fused": (_I, [_I64]),
     "gdsp_fft_batch": (_I, [_P, _P, _I64, _I64, _I]),
     "gdsp_fft_real_batch": (_I, [_P, _P, _I64, _I64]),
     "gdsp_fft2": (_I, [_P, _P, _I64, _I64, _I]),

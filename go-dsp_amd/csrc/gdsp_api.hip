@@ -82,7 +82,7 @@ constexpr unsigned kAlgoAll = GDSP_ALGO_GENERIC_MIXED | GDSP_ALGO_NO_CHIRPZ_PART
                               GDSP_ALGO_NO_FUSED_CONVOLVE | GDSP_ALGO_NO_FUSED_PWELCH_BATCH |
                               GDSP_ALGO_NO_FUSED_CPSD | GDSP_ALGO_NO_FUSED_FIR |
                               GDSP_ALGO_NO_FUSED_STFT | GDSP_ALGO_NO_FUSED_ISTFT |
-                              GDSP_ALGO_NO_FUSED_UPFIRDN;
+                              GDSP_ALGO_NO_FUSED_UPFIRDN | GDSP_ALGO_NO_FUSED_HILBERT;
 
 // Scratch device memory: a grow-only buffer per (device, stream, use-site
 // slot), allocated with hipMalloc. Reuse is ordered by the stream itself: a
@@ -1359,6 +1359,132 @@ int gdsp_upfirdn_batch(const double *x, int64_t ldx, const double *h, int64_t m,
     }));
     // returns after the stream drained: the next chunk may reuse the buffers
     STCHK(unstage_rows(out + (jb - out_begin), po, channels, cnt, ldo, s));
+  }
+  return GDSP_OK;
+}
+
+// ---- the analytic signal of real rows (hilbert.hip) ---------------------------
+// samples of one chunk of the host entry and of the composed form (all rows
+// together)
+static constexpr int64_t HILBERT_CHUNK_ELEMS = (int64_t)1 << 24;
+
+static bool hilbert_fused(int64_t N) {
+  return gdsp::hilbert_lds_applies(N) && !(g_algo.load() & GDSP_ALGO_NO_FUSED_HILBERT);
+}
+
+int gdsp_hilbert_fused(int64_t nfft) { return nfft > 0 && hilbert_fused(nfft) ? 1 : 0; }
+
+// rows of the composed form's chunk
+static int64_t hilbert_chunk_rows(int64_t N, int64_t rows) {
+  int64_t r = HILBERT_CHUNK_ELEMS / N;
+  if (r < 1) r = 1;
+  return r < rows ? r : rows;
+}
+
+// Argument checks shared by the host and device entries, in the order of the
+// header's table, up to the NULL pointers; *done: nothing to do; *N: the
+// transform length. No device call is made.
+static int hilbert_check(const void *x, int64_t ldx, int64_t rows, int64_t n, int64_t nfft,
+                         int kind, const void *out, int64_t ldo, int64_t *N, bool *done) {
+  *done = false;
+  if (rows < 0 || n < 0 || nfft < 0) return fail(GDSP_ERR_INVALID, "negative size");
+  if (kind < GDSP_HILBERT_ANALYTIC || kind > GDSP_HILBERT_ENVELOPE)
+    return fail(GDSP_ERR_INVALID, "kind must be 0, 1 or 2");
+  *N = nfft == 0 ? n : nfft;
+  if (rows > 1 && (ldx < n || ldo < *N))
+    return fail(GDSP_ERR_INVALID, "row stride below the row length");
+  if (rows == 0) {
+    *done = true;
+    return GDSP_OK;
+  }
+  if (n == 0 || *N == 0) return fail(GDSP_ERR_EMPTY, "empty input array");
+  if (!x || !out) return fail(GDSP_ERR_INVALID, "NULL pointer");
+  return GDSP_OK;
+}
+
+// work (NULL: the workspace pool): nothing in the fused form; composed,
+// hilbert_chunk_rows(N, rows) rows of N complex128, then as many of N float64
+static int hilbert_rows(const double *d_x, int64_t ldx, int64_t rows, int64_t n, int64_t N,
+                        int kind, void *d_out, int64_t ldo, void *work, hipStream_t s) {
+  gdsp_plan *p = nullptr;
+  STCHK(get_plan(N, &p));
+  // a power of 2 up to 2^14 is KIND_LDS under every flag set (fir_rows); the
+  // kind is checked because the kernel reads that plan's twiddle table
+  if (hilbert_fused(N) && p->kind == KIND_LDS) {
+    HIPCHK(gdsp::launch_hilbert_lds(p->log2n, kind, d_x, ldx, rows, n, d_out, ldo, p->tw, s));
+    return GDSP_OK;
+  }
+  const int64_t cr = hilbert_chunk_rows(N, rows);
+  DevBuf w;
+  if (!work) {
+    STCHK(w.alloc((size_t)cr * (size_t)N * (sizeof(cd) + sizeof(double)), s, SLOT_HB));
+    work = w.p;
+  }
+  cd *spec = (cd *)work;
+  double *buf = (double *)(spec + cr * N);
+  for (int64_t r0 = 0; r0 < rows; r0 += cr) {
+    later_chunk(r0);
+    const int64_t cnt = rows - r0 < cr ? rows - r0 : cr;
+    if (N == 1) {  // h = 0
+      HIPCHK(gdsp::launch_hilbert_store(kind, d_x, ldx, r0, cnt, n, N, nullptr, d_out, ldo, s));
+      continue;
+    }
+    HIPCHK(gdsp::launch_hilbert_gather(d_x, ldx, r0, cnt, n, N, buf, s));
+    STCHK(exec_plan(p, buf, spec, cnt, false, gdsp::LOAD_REAL, s));
+    HIPCHK(gdsp::launch_hilbert_mask(spec, cnt, N, s));
+    STCHK(exec_plan(p, spec, spec, cnt, true, gdsp::LOAD_COMPLEX, s));
+    HIPCHK(gdsp::launch_hilbert_store(kind, d_x, ldx, r0, cnt, n, N, spec, d_out, ldo, s));
+  }
+  return GDSP_OK;
+}
+
+int gdsp_hilbert_batch_device(const void *d_x, int64_t ldx, int64_t rows, int64_t n,
+                              int64_t nfft, int kind, void *d_out, int64_t ldo, void *d_work,
+                              void *stream) {
+  int64_t N = 0;
+  bool done = false;
+  STCHK(hilbert_check(d_x, ldx, rows, n, nfft, kind, d_out, ldo, &N, &done));
+  if (done) return GDSP_OK;
+  if (rows == 1) ldx = n, ldo = N;
+  // the kinds that store the input read it again while other workgroups store
+  const uintptr_t esz = kind == GDSP_HILBERT_ANALYTIC ? sizeof(cd) : sizeof(double);
+  const uintptr_t xa = (uintptr_t)d_x, oa = (uintptr_t)d_out;
+  const uintptr_t xe = xa + ((uintptr_t)(rows - 1) * (uintptr_t)ldx + (uintptr_t)n) * 8;
+  const uintptr_t oe = oa + ((uintptr_t)(rows - 1) * (uintptr_t)ldo + (uintptr_t)N) * esz;
+  if (xa < oe && oa < xe) return fail(GDSP_ERR_INVALID, "d_out overlaps d_x");
+  return hilbert_rows((const double *)d_x, ldx, rows, n, N, kind, d_out, ldo, d_work,
+                      (hipStream_t)stream);
+}
+
+int gdsp_hilbert_batch(const double *x, int64_t ldx, int64_t rows, int64_t n, int64_t nfft,
+                       int kind, double *out, int64_t ldo) {
+  int64_t N = 0;
+  bool done = false;
+  STCHK(hilbert_check(x, ldx, rows, n, nfft, kind, out, ldo, &N, &done));
+  if (done) return GDSP_OK;
+  int dev = 0;
+  STCHK(current_device(&dev));
+  hipStream_t s = thread_stream(dev);
+  if (!s) return fail(GDSP_ERR_HIP, "stream creation failed");
+  const int64_t nn = n < N ? n : N;                         // the samples a row gives
+  const int64_t od = kind == GDSP_HILBERT_ANALYTIC ? 2 : 1;  // doubles per output element
+  if (rows == 1) ldx = n, ldo = N;
+  // row ranges that start at even rows
+  int64_t rng = (HILBERT_CHUNK_ELEMS / N) & ~(int64_t)1;
+  if (rng < 2) rng = 2;
+  DevBuf dx, dout;
+  for (int64_t r0 = 0; r0 < rows; r0 += rng) {
+    later_chunk(r0);
+    const int64_t cnt = rows - r0 < rng ? rows - r0 : rng;
+    STCHK(dx.alloc((size_t)cnt * (size_t)nn * sizeof(double), s, SLOT_IN));
+    STCHK(dout.alloc((size_t)cnt * (size_t)N * (size_t)od * sizeof(double), s, SLOT_HB_OUT));
+    double *px = (double *)dx.p, *po = (double *)dout.p;
+    STCHK(run_queued(s, [&]() -> int {
+      STCHK(stage_rows(px, x + r0 * ldx, cnt, nn, ldx, nn, s));
+      return hilbert_rows(px, nn, cnt, nn, N, kind, po, N, nullptr, s);
+    }));
+    // returns after the stream drained: the next chunk may reuse the buffers
+    STCHK(unstage_rows(out + r0 * ldo * od, po, cnt, N * od, ldo * od, s));
   }
   return GDSP_OK;
 }

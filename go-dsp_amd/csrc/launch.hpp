@@ -385,6 +385,24 @@ hipError_t launch_upfirdn_plain(const double *x, int64_t ldx, int64_t x_lo, int6
                                 const double *hp, int64_t m, int64_t up, int64_t down,
                                 int64_t channels, int64_t out_begin, int64_t out_end, double *out,
                                 int64_t ldo, hipStream_t s);
+// The analytic signal of real rows (hilbert.hip): row r of x (n samples, ldx
+// apart) cut or zero-padded to N, h = IFFT_N(m FFT_N(x)) with the Hilbert
+// multiplier m, stored N elements per row, ldo output elements apart: kind 0
+// complex128 x + i h, 1 float64 h, 2 float64 sqrt(fma(x, x, h h)). The fused
+// kernel: N = 2^log2n where hilbert_lds_applies(N), one row per transform, tw
+// the KIND_LDS plan's table; out must not overlap x. The composed form's
+// kernels for any N, rows [r0, r0 + cnt): padded real rows of N into buf, the
+// multiplier on cnt spectra in place, and the store from the inverse
+// transform's real parts (spec; NULL: h = 0).
+bool hilbert_lds_applies(int64_t N);
+hipError_t launch_hilbert_lds(int log2n, int kind, const double *x, int64_t ldx, int64_t rows,
+                              int64_t n, void *out, int64_t ldo, const cd *tw, hipStream_t s);
+hipError_t launch_hilbert_gather(const double *x, int64_t ldx, int64_t r0, int64_t cnt, int64_t n,
+                                 int64_t N, double *buf, hipStream_t s);
+hipError_t launch_hilbert_mask(cd *spec, int64_t cnt, int64_t N, hipStream_t s);
+hipError_t launch_hilbert_store(int kind, const double *x, int64_t ldx, int64_t r0, int64_t cnt,
+                                int64_t n, int64_t N, const cd *spec, void *out, int64_t ldo,
+                                hipStream_t s);
 // wav.ReadFloats conversion (wav.hip): audio_format 1 (bits 8 / 16) or 3
 hipError_t launch_wav_decode(const void *in, int64_t count, int audio_format, int bits,
                              void *out, bool f64, hipStream_t s);

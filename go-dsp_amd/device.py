@@ -198,6 +198,47 @@ def upfirdn_batch(x, h, up: int = 1, down: int = 1, out=None, out_begin: int = 0
     return out
 
 
+_HILBERT_KINDS = {"analytic": _lib.GDSP_HILBERT_ANALYTIC, "quadrature": _lib.GDSP_HILBERT_QUADRATURE,
+                  "envelope": _lib.GDSP_HILBERT_ENVELOPE}
+
+
+def hilbert_batch(x, N=None, kind: str = "analytic", out=None, work=None, stream=None):
+    """fft.HilbertBatch on a float64 CUDA tensor (rows, n; unit inner stride,
+    any row stride): every row cut or zero-padded to N samples (None: n) and
+    its analytic signal x + i h (kind "analytic": complex128), h alone
+    ("quadrature": float64) or sqrt(fma(x, x, h h)) ("envelope": float64) into
+    out (rows, N; unit inner stride, any row stride), which must not overlap
+    x and is allocated only when not given. work: scratch (any dtype) of the
+    bytes gdsp_hilbert_batch_device states for the composed form; the fused
+    form (fft.hilbert_fused(N)) takes none, and with work given neither
+    allocates nor synchronises."""
+    torch = _torch()
+    assert x.is_cuda and x.dtype == torch.float64 and x.dim() == 2
+    k = _HILBERT_KINDS[kind]
+    rows, n = x.shape
+    nfft = n if N is None else int(N)
+    dt = torch.complex128 if k == _lib.GDSP_HILBERT_ANALYTIC else torch.float64
+    if out is None:
+        out = torch.empty((rows, max(nfft, 0)), dtype=dt, device=x.device)
+    assert out.is_cuda and out.dtype == dt and out.device == x.device
+    assert tuple(out.shape) == (rows, max(nfft, 0))
+    assert n == 0 or x.stride(1) == 1, "rows must have unit inner stride"
+    assert nfft <= 0 or out.stride(1) == 1, "rows must have unit inner stride"
+    ldx = x.stride(0) if rows > 1 else n
+    ldo = out.stride(0) if rows > 1 else nfft
+    if work is not None:
+        assert work.is_cuda and work.device == x.device and work.is_contiguous()
+        if nfft > 0 and not lib().gdsp_hilbert_fused(nfft):
+            need = min(rows, max(1, (1 << 24) // nfft)) * nfft * 24
+            assert work.numel() * work.element_size() >= need and work.data_ptr() % 16 == 0
+    with torch.cuda.device(x.device):
+        wp = _ptr(work) if work is not None else ctypes.c_void_p()
+        check(lib().gdsp_hilbert_batch_device(_ptr(x), ldx, rows, n, nfft, k, _ptr(out), ldo, wp,
+                                              _stream_ptr(stream, x.device)),
+              "hilbert_batch_device")
+    return out
+
+
 def resample_poly_batch(x, up: int, down: int, taps=None, out=None, stream=None):
     """fft.ResamplePolyBatch on a float64 CUDA tensor (channels, n):
     scipy.signal.resample_poly(x, up, down, axis=1) with its default zero

@@ -204,6 +204,54 @@ def Upfirdn(x, h, up: int = 1, down: int = 1) -> np.ndarray:
     return UpfirdnBatch(np.asarray(x, dtype=np.float64).reshape(1, -1), h, up, down)[0]
 
 
+def hilbert_fused(N: int) -> bool:
+    """Whether HilbertBatch runs transform length N on the fused
+    analytic-signal kernel under the current algorithm flags
+    (gdsp_hilbert_fused; host arithmetic)."""
+    return bool(lib().gdsp_hilbert_fused(int(N)))
+
+
+def _hilbert(rows, N, kind: int, what: str) -> np.ndarray:
+    x = _real_rows(rows, what)
+    r, n = x.shape
+    nfft = n if N is None else int(N)
+    if nfft < 0:
+        raise _lib.GDSPError(_lib.GDSP_ERR_INVALID, "negative size")
+    out = np.empty((r, nfft), np.complex128 if kind == _lib.GDSP_HILBERT_ANALYTIC else np.float64)
+    check(lib().gdsp_hilbert_batch(_p(x), n, r, n, nfft, kind, _p(out), nfft), what)
+    return out
+
+
+def HilbertBatch(rows, N=None) -> np.ndarray:
+    """Additive analytic signal of every row of the real (rows, n) array (or
+    list of rows): scipy.signal.hilbert(rows, N, axis=1) — each row cut or
+    zero-padded to N samples (None: n), x + i h with h the row's Hilbert
+    transform; complex128 (rows, N). The real part is the input's own bits."""
+    return _hilbert(rows, N, _lib.GDSP_HILBERT_ANALYTIC, "HilbertBatch")
+
+
+def Hilbert(x, N=None) -> np.ndarray:
+    """scipy.signal.hilbert(x, N) of the real signal x (HilbertBatch of one
+    row)."""
+    if np.iscomplexobj(x):
+        raise TypeError("Hilbert: complex input is not supported")
+    return HilbertBatch(np.asarray(x, dtype=np.float64).reshape(1, -1), N)[0]
+
+
+def EnvelopeBatch(rows, N=None) -> np.ndarray:
+    """abs(scipy.signal.hilbert(rows, N, axis=1)) as sqrt(fma(x, x, h h)):
+    float64 (rows, N), computed where the analytic signal is, without storing
+    it."""
+    return _hilbert(rows, N, _lib.GDSP_HILBERT_ENVELOPE, "EnvelopeBatch")
+
+
+def Envelope(x, N=None) -> np.ndarray:
+    """The envelope of the real signal x (EnvelopeBatch of one row)."""
+    if np.iscomplexobj(x):
+        raise TypeError("Envelope: complex input is not supported")
+    return EnvelopeBatch(np.asarray(x, dtype=np.float64).reshape(1, -1), N)[0]
+
+
 def _rate_pair(up: int, down: int) -> tuple[int, int]:
     import math
     up, down = int(up), int(down)
@@ -420,6 +468,7 @@ ALGO_NO_FUSED_FIR = _lib.GDSP_ALGO_NO_FUSED_FIR
 ALGO_NO_FUSED_STFT = 1024
 ALGO_NO_FUSED_ISTFT = 4096  # 2048 is not a flag
 ALGO_NO_FUSED_UPFIRDN = 8192
+ALGO_NO_FUSED_HILBERT = 32768  # 16384 is not a flag
 
 
 def SetAlgorithm(flags: int = ALGO_DEFAULT) -> None:

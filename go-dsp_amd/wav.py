@@ -308,6 +308,26 @@ def FilterChannels(w: Wav, frames: int, h, full: bool = False):
     return out.cpu().numpy()
 
 
+def EnvelopeChannels(w: Wav, frames: int, N=None):
+    """The envelope of every channel of a multi-channel file: the next
+    `frames` frames of w, decoded planar on the GPU as for FilterChannels and
+    run through device.hilbert_batch(kind="envelope") at transform length N
+    (None: frames). Returns a (NumChannels, N) numpy array; row c equals
+    fft.EnvelopeBatch of channel c's decoded samples."""
+    import torch
+
+    from . import device
+    C = int(w.NumChannels)
+    raw, _ = w._read_raw(frames * C)
+    nfft = frames if N is None else int(N)
+    if frames == 0 or nfft == 0:
+        raise _lib.Panic(_lib.GDSP_ERR_EMPTY, "empty input array")
+    dev = torch.device("cuda", torch.cuda.current_device())
+    rd = torch.frombuffer(bytearray(raw), dtype=torch.uint8).to(dev)
+    x = device_floats_planar(rd, frames, C, w.AudioFormat, w.BitsPerSample)
+    return device.hilbert_batch(x, nfft, kind="envelope").cpu().numpy()
+
+
 def ResampleChannels(w: Wav, frames: int, rate: int):
     """Every channel of a multi-channel file at the sample rate `rate`: the
     next `frames` frames of w, decoded planar on the GPU as for FilterChannels

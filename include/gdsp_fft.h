@@ -128,7 +128,13 @@ enum {
   /* gdsp_upfirdn_batch / gdsp_upfirdn_batch_device on the plain form (one
    * thread per output, taps and samples from global memory) also for the
    * shapes the fused polyphase kernel serves. Read when the call is made. */
-  GDSP_ALGO_NO_FUSED_UPFIRDN = 8192
+  GDSP_ALGO_NO_FUSED_UPFIRDN = 8192,
+  /* gdsp_hilbert_batch / gdsp_hilbert_batch_device on the composed form
+   * (gathered real rows, the plan's real-row transform, the multiplier, the
+   * plan's inverse, a store kernel) also for the powers of 2 the fused
+   * analytic-signal kernel serves. Read when the call is made. The bit 16384
+   * is not used, like 2048: both stay unknown bits. */
+  GDSP_ALGO_NO_FUSED_HILBERT = 32768
 };
 /* Unknown bits → GDSP_ERR_INVALID (the selection is left unchanged). */
 int gdsp_set_algorithm(unsigned flags);
@@ -184,7 +190,17 @@ unsigned gdsp_get_algorithm(void);
  *                             gives +0.0; every output is summed in ascending t
  *                             with one fused multiply-add per term, so its bits
  *                             do not depend on the range, chunk, tile or form
- *                             that computes it (tests/test_resample_gpu.py) */
+ *                             that computes it (tests/test_resample_gpu.py)
+ *      Hilbert               every output of that row (analytic: the imaginary
+ *                             part; the real part is the input's bits), and no
+ *                             bit of any other row: both forms run one row
+ *                             per transform, so a row's outputs depend on that
+ *                             row alone, whatever its neighbours hold and
+ *                             however a job is cut into calls. A row of exact
+ *                             zeros gives exact zeros; a quiet row beside a
+ *                             loud one keeps its own relative accuracy; rows
+ *                             times 2^k give outputs times 2^k
+ *                             (tests/test_hilbert_gpu.py) */
 
 /* ---- fft package: host pointers, synchronous ----------------------------- */
 
@@ -291,6 +307,42 @@ int64_t gdsp_upfirdn_length(int64_t n, int64_t m, int64_t up, int64_t down);
  * for sizes the call refuses, and under GDSP_ALGO_NO_FUSED_UPFIRDN). Host
  * arithmetic on committed constants, no GPU needed. */
 int gdsp_upfirdn_fused(int64_t m, int64_t up, int64_t down);
+
+/* Additive analytic signal of real rows (no reference equivalent;
+ * scipy.signal.hilbert(x, N)): for `rows` rows of n float64, row r at x +
+ * r*ldx, and a transform length N (nfft; 0: n), row r is cut to N samples or
+ * padded with zeros to N, and
+ *   h_r = IFFT_N(m * FFT_N(x_r)),  m[f] = -i for 0 < f < N/2, +i for N/2 < f <
+ *   N, 0 at f = 0 and (N even) at f = N/2; h_r is real.
+ * N elements per row go to out + r*ldo:
+ *   GDSP_HILBERT_ANALYTIC    complex128 x_r[i] + i h_r[i]; the real part is the
+ *                            input sample's own bits (+0.0 in the padding)
+ *   GDSP_HILBERT_QUADRATURE  float64 h_r[i]
+ *   GDSP_HILBERT_ENVELOPE    float64 sqrt(fma(x, x, h*h))
+ * ldx in doubles, ldo in output elements (complex128 for ANALYTIC). Where
+ * gdsp_hilbert_fused(N), one kernel per call: a row as one complex transform
+ * (z = x + 0i), the multiplier as a swap of re and im, the inverse, the
+ * store; otherwise the composed form (gathered rows, the plan's real-row
+ * transform, the multiplier, the plan's inverse, a store kernel) in chunks of
+ * at most 2^24 samples. Longer host jobs are cut into ranges of rows that
+ * start at even rows, of at most 2^24 samples (HILBERT_CHUNK_ELEMS); a row's
+ * bits do not depend on the range it falls in.
+ * In this order, before any device call: a negative size, a kind outside
+ * 0..2, or, with rows > 1, ldx < n or ldo < N -> GDSP_ERR_INVALID; rows == 0 ->
+ * GDSP_OK, nothing done; n == 0 or N == 0 -> GDSP_ERR_EMPTY; a NULL pointer ->
+ * GDSP_ERR_INVALID. Runs on the current device. */
+enum {
+  GDSP_HILBERT_ANALYTIC = 0,
+  GDSP_HILBERT_QUADRATURE = 1,
+  GDSP_HILBERT_ENVELOPE = 2
+};
+int gdsp_hilbert_batch(const double *x, int64_t ldx, int64_t rows, int64_t n, int64_t nfft,
+                       int kind, double *out, int64_t ldo);
+/* 1 where the fused analytic-signal kernel serves transform length nfft under
+ * the current flags (a power of 2 from 256 to 16384, without
+ * GDSP_ALGO_NO_FUSED_HILBERT), 0 where the composed form runs. Host arithmetic
+ * only, no GPU needed. */
+int gdsp_hilbert_fused(int64_t nfft);
 
 /* Additive batched entry point (no reference equivalent): the
  * same transform as fft.FFT / fft.IFFT applied to `batch` contiguous rows of n
@@ -581,7 +633,8 @@ int gdsp_multi_stats(int64_t *batch_calls, int64_t *pwelch_calls, int64_t *rccl_
  * of gdsp_stft_batch / gdsp_spectrogram_batch and the channel and segment runs
  * of their materialised form, the output ranges of gdsp_istft_batch and the
  * channel and segment runs of its materialised form, the composed FIR's
- * transform chunks, the output ranges of gdsp_upfirdn_batch, and the
+ * transform chunks, the output ranges of gdsp_upfirdn_batch, the row ranges
+ * of gdsp_hilbert_batch and the row chunks of its composed form, and the
  * 65535-row pieces of gdsp_fft_axis_device / gdsp_fftn_device and of the
  * multi-pass, four-step and chirp-z executors).
  * multi_unit_launches: launches of a Pwelch, batched-Pwelch, Cpsd, STFT or ISTFT kernel
@@ -716,6 +769,20 @@ int gdsp_fir_batch_device(const void *d_x, int64_t ldx, const void *d_h, int64_t
 int gdsp_upfirdn_batch_device(const void *d_x, int64_t ldx, const void *d_h, int64_t m,
                               int64_t up, int64_t down, int64_t channels, int64_t n,
                               int64_t out_begin, int64_t out_end, void *d_out, int64_t ldo,
+                              void *d_work, void *stream);
+
+/* gdsp_hilbert_batch on device buffers (no reference equivalent),
+ * stream-ordered: d_x rows of n float64 at stride ldx (doubles), d_out rows of
+ * N output elements at stride ldo (output elements: complex128 for
+ * GDSP_HILBERT_ANALYTIC, float64 otherwise). The address ranges of d_x and
+ * d_out must not overlap (the kinds that store the input read it again while
+ * other workgroups store): GDSP_ERR_INVALID, decided after gdsp_hilbert_batch's
+ * own checks. d_work (may be NULL: the library's workspace pool): nothing
+ * where gdsp_hilbert_fused(N) (the fused call then neither allocates nor
+ * synchronises); otherwise R * N * 24 bytes, R = min(rows, max(1, 2^24 div
+ * N)): R rows of N complex128, then R rows of N float64, 16-byte aligned. */
+int gdsp_hilbert_batch_device(const void *d_x, int64_t ldx, int64_t rows, int64_t n,
+                              int64_t nfft, int kind, void *d_out, int64_t ldo,
                               void *d_work, void *stream);
 
 /* FFT2/IFFT2 on a device rows×cols complex128 matrix. d_work: scratch of
