@@ -71,6 +71,16 @@ SIGNATURES = {
     "gdsp_hilbert_batch": (_I, [_P, _I64, _I64, _I64, _I64, _I, _P, _I64]),
     "gdsp_hilbert_batch_device": (_I, [_P, _I64, _I64, _I64, _I64, _I, _P, _I64, _P, _P]),
     "gdsp_hilbert_fused": (_I, [_I64]),
+    "gdsp_sosfilt_batch": (_I, [_P, _I64, _P, _I64, _P, _I64, _I64, _P, _I64, _P]),
+    "gdsp_sosfilt_batch_device": (_I, [_P, _I64, _P, _I64, _P, _I64, _I64, _P, _I64, _P, _P, _P]),
+    "gdsp_sosfiltfilt_batch": (_I, [_P, _I64, _P, _I64, _I64, _I64, _I64, _P, _I64]),
+    "gdsp_sosfiltfilt_batch_device": (_I, [_P, _I64, _P, _I64, _I64, _I64, _I64, _P, _I64, _P, _P]),
+    "gdsp_sosfilt_fused": (_I, [_P, _I64]),
+    "gdsp_sosfilt_granule": (_I64, [_I64]),
+    "gdsp_sosfilt_zi": (_I, [_P, _I64, _P]),
+    "gdsp_sosfiltfilt_padlen": (_I64, [_P, _I64]),
+    "gdsp_sosfilt_work_doubles": (_I64, [_I64, _I64, _I64]),
+    "gdsp_sosfiltfilt_work_doubles": (_I64, [_I64, _I64, _I64, _I64]),
     "gdsp_fft_batch": (_I, [_P, _P, _I64, _I64, _I]),
     "gdsp_fft_real_batch": (_I, [_P, _P, _I64, _I64]),
     "gdsp_fft2": (_I, [_P, _P, _I64, _I64, _I]),

@@ -12,6 +12,7 @@
 
 #include <algorithm>
 #include <atomic>
+#include <functional>
 #include <map>
 #include <mutex>
 #include <string>
@@ -82,7 +83,8 @@ constexpr unsigned kAlgoAll = GDSP_ALGO_GENERIC_MIXED | GDSP_ALGO_NO_CHIRPZ_PART
                               GDSP_ALGO_NO_FUSED_CONVOLVE | GDSP_ALGO_NO_FUSED_PWELCH_BATCH |
                               GDSP_ALGO_NO_FUSED_CPSD | GDSP_ALGO_NO_FUSED_FIR |
                               GDSP_ALGO_NO_FUSED_STFT | GDSP_ALGO_NO_FUSED_ISTFT |
-                              GDSP_ALGO_NO_FUSED_UPFIRDN | GDSP_ALGO_NO_FUSED_HILBERT;
+                              GDSP_ALGO_NO_FUSED_UPFIRDN | GDSP_ALGO_NO_FUSED_HILBERT |
+                              GDSP_ALGO_NO_FUSED_SOSFILT;
 
 // Scratch device memory: a grow-only buffer per (device, stream, use-site
 // slot), allocated with hipMalloc. Reuse is ordered by the stream itself: a
@@ -1487,6 +1489,424 @@ int gdsp_hilbert_batch(const double *x, int64_t ldx, int64_t rows, int64_t n, in
     STCHK(unstage_rows(out + r0 * ldo * od, po, cnt, N * od, ldo * od, s));
   }
   return GDSP_OK;
+}
+
+// ---- recursive filtering of real rows (sosfilt.hip) ---------------------------
+// samples of one chunk of the host entries (all rows together)
+static constexpr int64_t SOSFILT_CHUNK_ELEMS = (int64_t)1 << 25;
+
+static bool sos_coeffs_ok(const double *sos, int64_t S) {
+  for (int64_t i = 0; i < 6 * S; ++i)
+    if (!std::isfinite(sos[i])) return false;
+  for (int64_t s = 0; s < S; ++s)
+    if (sos[6 * s + 3] != 1.0) return false;
+  return true;
+}
+
+int gdsp_sosfilt_fused(const double *sos, int64_t S) {
+  if (!sos || S < 1 || S > gdsp::kSosMaxFused || (g_algo.load() & GDSP_ALGO_NO_FUSED_SOSFILT))
+    return 0;
+  if (!sos_coeffs_ok(sos, S)) return 0;
+  for (int64_t s = 0; s < S; ++s) {
+    const double a1 = sos[6 * s + 4], a2 = sos[6 * s + 5];
+    if (!(fabs(a2) < 1.0 && fabs(a1) < 1.0 + a2)) return 0;
+  }
+  return 1;
+}
+
+int64_t gdsp_sosfilt_granule(int64_t S) {
+  return S >= 1 && S <= gdsp::kSosMaxSections ? gdsp::kSosTile : 0;
+}
+
+int gdsp_sosfilt_zi(const double *sos, int64_t S, double *zi) {
+  if (S < 0) return fail(GDSP_ERR_INVALID, "negative size");
+  if (S == 0) return GDSP_OK;
+  if (!sos || !zi) return fail(GDSP_ERR_INVALID, "NULL pointer");
+  if (!sos_coeffs_ok(sos, S)) return fail(GDSP_ERR_INVALID, "a0 must be 1, coefficients finite");
+  long double scale = 1.0L;
+  for (int64_t s = 0; s < S; ++s) {
+    const long double b0 = sos[6 * s], b1 = sos[6 * s + 1], b2 = sos[6 * s + 2],
+                      a1 = sos[6 * s + 4], a2 = sos[6 * s + 5];
+    const long double den = 1.0L + a1 + a2;
+    if (den == 0.0L) return fail(GDSP_ERR_INVALID, "a section with a pole at z = 1");
+    const long double gain = (b0 + b1 + b2) / den;  // the step response settles at it
+    const long double z1 = b2 - a2 * gain, z0 = b1 - a1 * gain + z1;
+    zi[2 * s] = (double)(scale * z0);
+    zi[2 * s + 1] = (double)(scale * z1);
+    scale *= gain;
+  }
+  return GDSP_OK;
+}
+
+int64_t gdsp_sosfiltfilt_padlen(const double *sos, int64_t S) {
+  if (!sos || S < 1 || S > gdsp::kSosMaxSections) return -1;
+  int64_t zb = 0, za = 0;
+  for (int64_t s = 0; s < S; ++s) {
+    zb += sos[6 * s + 2] == 0.0;
+    za += sos[6 * s + 5] == 0.0;
+  }
+  return 3 * (2 * S + 1 - (zb < za ? zb : za));
+}
+
+// doubles of device scratch a launch over rows of n samples takes: the tables,
+// then per row the end and entry states of its tiles
+static int64_t sos_work_doubles(int64_t S, int64_t channels, int64_t n) {
+  const int64_t T = (n + gdsp::kSosTile - 1) / gdsp::kSosTile;
+  return gdsp::kSosTableDoubles + channels * (2 * T + 1) * 2 * S;
+}
+
+int64_t gdsp_sosfilt_work_doubles(int64_t S, int64_t channels, int64_t n) {
+  if (S < 1 || S > gdsp::kSosMaxSections || channels < 0 || n < 0) return -1;
+  return sos_work_doubles(S, channels, n);
+}
+
+int64_t gdsp_sosfiltfilt_work_doubles(int64_t S, int64_t channels, int64_t n, int64_t padlen) {
+  if (S < 1 || S > gdsp::kSosMaxSections || channels < 0 || n < 0 || padlen < 0) return -1;
+  const int64_t L = n + 2 * padlen;
+  return sos_work_doubles(S, channels, L) + 2 * S + channels * 2 * S + channels * L;
+}
+
+namespace {
+
+typedef long double ld_t;
+
+// c = a b, square matrices of order m
+void sos_matmul(const ld_t *a, const ld_t *b, ld_t *c, int m) {
+  for (int i = 0; i < m; ++i)
+    for (int j = 0; j < m; ++j) {
+      ld_t acc = 0;
+      for (int k = 0; k < m; ++k) acc += a[i * m + k] * b[k * m + j];
+      c[i * m + j] = acc;
+    }
+}
+
+// The time-parallel form's tables (launch.hpp), in long double, rounded once.
+void sos_build_tables(const double *sos, int S, double *t) {
+  using namespace gdsp;
+  for (int i = 0; i < kSosTableDoubles; ++i) t[i] = 0.0;
+  for (int s = 0; s < S; ++s) {
+    double *ts = t + s * kSosSecDoubles;
+    const double *q = sos + 6 * s;
+    ts[0] = q[0], ts[1] = q[1], ts[2] = q[2], ts[3] = q[4], ts[4] = q[5];
+    // zero input: y = z0; z0' = -a1 z0 + z1; z1' = -a2 z0
+    const ld_t A[4] = {-(ld_t)q[4], 1, -(ld_t)q[5], 0};
+    ld_t P[4] = {1, 0, 0, 1}, N[4];
+    for (int i = 0; i < kSosE; ++i) {  // P = A^i: its first row is output i
+      ts[8 + 2 * i] = (double)P[0], ts[8 + 2 * i + 1] = (double)P[1];
+      sos_matmul(A, P, N, 2);
+      for (int e = 0; e < 4; ++e) P[e] = N[e];
+    }
+    for (int k = 0; k < 7; ++k) {  // P = M^(2^k)
+      for (int e = 0; e < 4; ++e) ts[8 + 2 * kSosE + 4 * k + e] = (double)P[e];
+      sos_matmul(P, P, N, 2);
+      for (int e = 0; e < 4; ++e) P[e] = N[e];
+    }
+  }
+  // one step of the whole cascade on zero input, column by column
+  const int m = 2 * S;
+  std::vector<ld_t> A((size_t)m * m, 0), B((size_t)m * m);
+  for (int j = 0; j < m; ++j) {
+    ld_t y = 0;  // the cascade's input
+    for (int s = 0; s < S; ++s) {
+      const double *q = sos + 6 * s;
+      const ld_t z0 = j == 2 * s, z1 = j == 2 * s + 1, xin = y;
+      y = (ld_t)q[0] * xin + z0;
+      A[(2 * s) * m + j] = (ld_t)q[1] * xin - (ld_t)q[4] * y + z1;
+      A[(2 * s + 1) * m + j] = (ld_t)q[2] * xin - (ld_t)q[5] * y;
+    }
+  }
+  for (int64_t len = 1; len < kSosTile; len *= 2) {
+    sos_matmul(A.data(), A.data(), B.data(), m);
+    A.swap(B);
+  }
+  for (int i = 0; i < m * m; ++i) t[kSosPhiOffset + i] = (double)A[i];
+}
+
+// The tables of the last filter a thread used: building them is host work of
+// a twelve-fold squaring of a 2 S x 2 S matrix.
+const double *sos_tables_cached(const double *sos, int S) {
+  thread_local int cs = 0;
+  thread_local double key[6 * gdsp::kSosMaxFused], tab[gdsp::kSosTableDoubles];
+  if (cs != S || memcmp(key, sos, (size_t)S * 6 * sizeof(double)) != 0) {
+    sos_build_tables(sos, S, tab);
+    memcpy(key, sos, (size_t)S * 6 * sizeof(double));
+    cs = S;
+  }
+  return tab;
+}
+
+// The filter's tables into work (once per call), then launches over them.
+int sos_upload(const double *sos, int S, bool fused, double *work, hipStream_t s) {
+  if (fused) {
+    HIPCHK(gdsp::launch_sos_tables(sos_tables_cached(sos, S), gdsp::kSosTableDoubles, work, s));
+  } else {
+    double coef[5 * gdsp::kSosMaxSections];
+    for (int i = 0; i < S; ++i) {
+      const double *q = sos + 6 * i;
+      double *c = coef + 5 * i;
+      c[0] = q[0], c[1] = q[1], c[2] = q[2], c[3] = q[4], c[4] = q[5];
+    }
+    HIPCHK(gdsp::launch_sos_tables(coef, 5 * S, work, s));
+  }
+  return GDSP_OK;
+}
+
+int sos_run(const gdsp::SosIo &io, int S, bool fused, int64_t channels, const double *d_zi,
+            double *d_zf, double *work, hipStream_t s) {
+  if (fused) {
+    HIPCHK(gdsp::launch_sos_tiles(io, work, S, channels, d_zi, d_zf,
+                                  work + gdsp::kSosTableDoubles, s));
+  } else {
+    HIPCHK(gdsp::launch_sos_plain(io, work, S, channels, d_zi, d_zf, s));
+  }
+  return GDSP_OK;
+}
+
+gdsp::SosIo sos_io_plain(const double *src, int64_t lds, double *dst, int64_t ldd, int64_t n) {
+  gdsp::SosIo io = {};
+  io.src = src, io.lds = lds, io.dst = dst, io.ldd = ldd, io.n = n, io.nx = n;
+  io.mode = gdsp::SOS_IO_PLAIN;
+  return io;
+}
+
+// Argument checks shared by the host and device entries, in the order of the
+// header's table; *done: nothing to do. padlen: -2 for sosfilt; else
+// sosfiltfilt's (-1: the default), resolved into *pl. No device call is made.
+int sos_check(const void *x, int64_t ldx, const double *sos, int64_t S, int64_t padlen,
+              int64_t channels, int64_t n, const void *out, int64_t ldo, int64_t *pl,
+              bool *done) {
+  *done = false;
+  if (S < 0 || channels < 0 || n < 0 || padlen < -2)
+    return fail(GDSP_ERR_INVALID, "negative size");
+  if (channels > 1 && (ldx < n || ldo < n))
+    return fail(GDSP_ERR_INVALID, "row stride below the row length");
+  if (channels == 0) {
+    *done = true;
+    return GDSP_OK;
+  }
+  if (n == 0 || S == 0) return fail(GDSP_ERR_EMPTY, "empty input array");
+  if (S > gdsp::kSosMaxSections) return fail(GDSP_ERR_UNSUPPORTED, "more than 64 sections");
+  if (!x || !sos || !out) return fail(GDSP_ERR_INVALID, "NULL pointer");
+  if (!sos_coeffs_ok(sos, S))
+    return fail(GDSP_ERR_INVALID, "a0 must be 1 and every coefficient finite");
+  if (padlen != -2) {
+    *pl = padlen == -1 ? gdsp_sosfiltfilt_padlen(sos, S) : padlen;
+    if (n <= *pl) return fail(GDSP_ERR_INVALID, "the rows must be longer than padlen");
+    if (*pl > ((int64_t)1 << 40) || n > INT64_MAX - 2 * *pl)
+      return fail(GDSP_ERR_INVALID, "padlen out of range");
+  }
+  return GDSP_OK;
+}
+
+bool sos_overlap(const void *a, int64_t lda, const void *b, int64_t ldb, int64_t rows, int64_t n) {
+  const uintptr_t xa = (uintptr_t)a, oa = (uintptr_t)b;
+  const uintptr_t xe = xa + ((uintptr_t)(rows - 1) * (uintptr_t)lda + (uintptr_t)n) * 8;
+  const uintptr_t oe = oa + ((uintptr_t)(rows - 1) * (uintptr_t)ldb + (uintptr_t)n) * 8;
+  return xa < oe && oa < xe;
+}
+
+// samples of a row per chunk of the host entries: a multiple of the granule
+int64_t sos_chunk_len(int64_t S, int64_t channels) {
+  const int64_t G = gdsp_sosfilt_granule(S);
+  int64_t rng = SOSFILT_CHUNK_ELEMS / channels / G * G;
+  return rng < G ? G : rng;
+}
+
+}  // namespace
+
+int gdsp_sosfilt_batch_device(const void *d_x, int64_t ldx, const double *sos, int64_t S,
+                              const void *d_zi, int64_t channels, int64_t n, void *d_out,
+                              int64_t ldo, void *d_zf, void *d_work, void *stream) {
+  bool done = false;
+  int64_t pl = 0;
+  STCHK(sos_check(d_x, ldx, sos, S, -2, channels, n, d_out, ldo, &pl, &done));
+  if (done) return GDSP_OK;
+  if (channels == 1) ldx = ldo = n;
+  // pass 3 reads a tile before it stores it, and tiles do not share samples:
+  // out may be x itself, and nothing else that overlaps it
+  if (!(d_x == d_out && ldx == ldo) && sos_overlap(d_x, ldx, d_out, ldo, channels, n))
+    return fail(GDSP_ERR_INVALID, "d_out overlaps d_x without being d_x");
+  int dev = 0;
+  STCHK(current_device(&dev));
+  hipStream_t s = (hipStream_t)stream;
+  DevBuf w;
+  double *work = (double *)d_work;
+  if (!work) {
+    STCHK(w.alloc((size_t)sos_work_doubles(S, channels, n) * sizeof(double), s, SLOT_SOS));
+    work = (double *)w.p;
+  }
+  const bool fused = gdsp_sosfilt_fused(sos, S) != 0;
+  STCHK(sos_upload(sos, (int)S, fused, work, s));
+  return sos_run(sos_io_plain((const double *)d_x, ldx, (double *)d_out, ldo, n), (int)S, fused,
+                 channels, (const double *)d_zi, (double *)d_zf, work, s);
+}
+
+// Host rows through the device in chunks of time, in place on the staged
+// chunk, the state carried in two device buffers that swap. make(v0, len, dst):
+// the chunk's samples as dense host rows, or NULL where the caller's rows
+// x + v0 serve; take(v0, len, src): dense device rows back to the caller.
+typedef std::function<int(int64_t, int64_t, double *)> SosStage;
+typedef std::function<int(int64_t, int64_t, const double *)> SosTake;
+static int sos_host_chunks(const double *sos, int64_t S, int64_t channels, int64_t n,
+                           const double *zi_host, double *zf_host, const SosStage &stage,
+                           const SosTake &take, hipStream_t s) {
+  const int64_t rng = sos_chunk_len(S, channels);
+  const int64_t first = n < rng ? n : rng;
+  const size_t zbytes = (size_t)channels * 2 * (size_t)S * sizeof(double);
+  DevBuf dx, dz, dw;
+  STCHK(dx.alloc((size_t)channels * (size_t)first * sizeof(double), s, SLOT_IN));
+  STCHK(dz.alloc(2 * zbytes, s, SLOT_SOS_Z));
+  STCHK(dw.alloc((size_t)sos_work_doubles(S, channels, first) * sizeof(double), s, SLOT_SOS));
+  double *px = (double *)dx.p, *za = (double *)dz.p, *zb = za + channels * 2 * S;
+  const bool fused = gdsp_sosfilt_fused(sos, S) != 0;
+  for (int64_t v0 = 0; v0 < n; v0 += rng) {
+    later_chunk(v0);
+    const int64_t len = n - v0 < rng ? n - v0 : rng;
+    const bool lastc = v0 + len == n;
+    STCHK(run_queued(s, [&]() -> int {
+      STCHK(stage(v0, len, px));
+      if (v0 == 0) {
+        STCHK(sos_upload(sos, (int)S, fused, (double *)dw.p, s));
+        if (zi_host) STCHK(copy_h2d(za, zi_host, zbytes, s));
+      }
+      return sos_run(sos_io_plain(px, len, px, len, len), (int)S, fused, channels,
+                     (v0 == 0 && !zi_host) ? nullptr : za, (lastc && !zf_host) ? nullptr : zb,
+                     (double *)dw.p, s);
+    }));
+    // returns after the stream drained: the next chunk may reuse the buffers
+    STCHK(take(v0, len, px));
+    std::swap(za, zb);
+  }
+  if (zf_host) STCHK(copy_d2h(zf_host, za, zbytes, s));
+  return GDSP_OK;
+}
+
+int gdsp_sosfilt_batch(const double *x, int64_t ldx, const double *sos, int64_t S,
+                       const double *zi, int64_t channels, int64_t n, double *out, int64_t ldo,
+                       double *zf) {
+  bool done = false;
+  int64_t pl = 0;
+  STCHK(sos_check(x, ldx, sos, S, -2, channels, n, out, ldo, &pl, &done));
+  if (done) return GDSP_OK;
+  int dev = 0;
+  STCHK(current_device(&dev));
+  hipStream_t s = thread_stream(dev);
+  if (!s) return fail(GDSP_ERR_HIP, "stream creation failed");
+  if (channels == 1) ldx = ldo = n;
+  return sos_host_chunks(
+      sos, S, channels, n, zi, zf,
+      [&](int64_t v0, int64_t len, double *px) -> int {
+        return stage_rows(px, x + v0, channels, len, ldx, len, s);
+      },
+      [&](int64_t v0, int64_t len, const double *px) -> int {
+        return unstage_rows(out + v0, px, channels, len, ldo, s);
+      },
+      s);
+}
+
+int gdsp_sosfiltfilt_batch_device(const void *d_x, int64_t ldx, const double *sos, int64_t S,
+                                  int64_t padlen, int64_t channels, int64_t n, void *d_out,
+                                  int64_t ldo, void *d_work, void *stream) {
+  bool done = false;
+  int64_t pl = 0;
+  if (padlen < -1) return fail(GDSP_ERR_INVALID, "negative size");
+  STCHK(sos_check(d_x, ldx, sos, S, padlen, channels, n, d_out, ldo, &pl, &done));
+  if (done) return GDSP_OK;
+  if (channels == 1) ldx = ldo = n;
+  if (sos_overlap(d_x, ldx, d_out, ldo, channels, n))
+    return fail(GDSP_ERR_INVALID, "d_out overlaps d_x");
+  double zi[2 * gdsp::kSosMaxSections];
+  STCHK(gdsp_sosfilt_zi(sos, S, zi));
+  int dev = 0;
+  STCHK(current_device(&dev));
+  hipStream_t s = (hipStream_t)stream;
+  DevBuf w;
+  double *work = (double *)d_work;
+  if (!work) {
+    STCHK(w.alloc((size_t)gdsp_sosfiltfilt_work_doubles(S, channels, n, pl) * sizeof(double), s,
+                  SLOT_SOS));
+    work = (double *)w.p;
+  }
+  const int64_t L = n + 2 * pl;
+  double *d_zi = work + sos_work_doubles(S, channels, L), *zrows = d_zi + 2 * S,
+         *mid = zrows + channels * 2 * S;
+  const bool fused = gdsp_sosfilt_fused(sos, S) != 0;
+  STCHK(sos_upload(sos, (int)S, fused, work, s));
+  HIPCHK(gdsp::launch_sos_tables(zi, 2 * S, d_zi, s));
+  // forward over the odd extension, which the loader forms
+  gdsp::SosIo fw = {};
+  fw.src = (const double *)d_x, fw.lds = ldx, fw.dst = mid, fw.ldd = L, fw.n = L, fw.nx = n;
+  fw.pad = pl, fw.mode = gdsp::SOS_IO_ODD_EXT;
+  HIPCHK(gdsp::launch_sos_ffzi(fw, 0, d_zi, (int)S, channels, zrows, s));
+  STCHK(sos_run(fw, (int)S, fused, channels, zrows, nullptr, work, s));
+  // backward over that, as far as the first sample kept
+  gdsp::SosIo bw = {};
+  bw.src = mid, bw.lds = L, bw.dst = (double *)d_out, bw.ldd = ldo, bw.n = L - pl, bw.nx = L;
+  bw.nout = n, bw.mode = gdsp::SOS_IO_REVERSED;
+  HIPCHK(gdsp::launch_sos_ffzi(bw, 0, d_zi, (int)S, channels, zrows, s));
+  return sos_run(bw, (int)S, fused, channels, zrows, nullptr, work, s);
+}
+
+int gdsp_sosfiltfilt_batch(const double *x, int64_t ldx, const double *sos, int64_t S,
+                           int64_t padlen, int64_t channels, int64_t n, double *out,
+                           int64_t ldo) {
+  bool done = false;
+  int64_t pl = 0;
+  if (padlen < -1) return fail(GDSP_ERR_INVALID, "negative size");
+  STCHK(sos_check(x, ldx, sos, S, padlen, channels, n, out, ldo, &pl, &done));
+  if (done) return GDSP_OK;
+  double zi[2 * gdsp::kSosMaxSections];
+  STCHK(gdsp_sosfilt_zi(sos, S, zi));
+  int dev = 0;
+  STCHK(current_device(&dev));
+  hipStream_t s = thread_stream(dev);
+  if (!s) return fail(GDSP_ERR_HIP, "stream creation failed");
+  if (channels == 1) ldx = ldo = n;
+  const int64_t L = n + 2 * pl, Lb = L - pl, S2 = 2 * S;
+  const int64_t rng = sos_chunk_len(S, channels);
+  // the intermediate of both passes stays in host memory
+  std::vector<double> mid((size_t)channels * (size_t)L), zrows((size_t)channels * (size_t)S2);
+  std::vector<double> buf((size_t)channels * (size_t)(L < rng ? L : rng));
+  // sample v of row c's odd extension, as the device entry's loader forms it
+  auto ext = [&](int64_t c, int64_t v) -> double {
+    const double *r = x + c * ldx;
+    const int64_t u = v - pl;
+    if (u < 0) return 2.0 * r[0] - r[-u];
+    if (u >= n) return 2.0 * r[n - 1] - r[2 * (n - 1) - u];
+    return r[u];
+  };
+  for (int64_t c = 0; c < channels; ++c)
+    for (int64_t j = 0; j < S2; ++j) zrows[c * S2 + j] = zi[j] * ext(c, 0);
+  STCHK(sos_host_chunks(
+      sos, S, channels, L, zrows.data(), nullptr,
+      [&](int64_t v0, int64_t len, double *px) -> int {
+        for (int64_t c = 0; c < channels; ++c)
+          for (int64_t i = 0; i < len; ++i) buf[c * len + i] = ext(c, v0 + i);
+        return stage_rows(px, buf.data(), channels, len, len, len, s);
+      },
+      [&](int64_t v0, int64_t len, const double *px) -> int {
+        return unstage_rows(mid.data() + v0, px, channels, len, L, s);
+      },
+      s));
+  for (int64_t c = 0; c < channels; ++c)
+    for (int64_t j = 0; j < S2; ++j) zrows[c * S2 + j] = zi[j] * mid[c * L + L - 1];
+  return sos_host_chunks(
+      sos, S, channels, Lb, zrows.data(), nullptr,
+      [&](int64_t v0, int64_t len, double *px) -> int {
+        for (int64_t c = 0; c < channels; ++c)
+          for (int64_t i = 0; i < len; ++i) buf[c * len + i] = mid[c * L + L - 1 - (v0 + i)];
+        return stage_rows(px, buf.data(), channels, len, len, len, s);
+      },
+      [&](int64_t v0, int64_t len, const double *px) -> int {
+        STCHK(unstage_rows(buf.data(), px, channels, len, len, s));
+        for (int64_t c = 0; c < channels; ++c)
+          for (int64_t i = 0; i < len; ++i) {
+            const int64_t j = Lb - 1 - (v0 + i);
+            if (j < n) out[c * ldo + j] = buf[c * len + i];
+          }
+        return GDSP_OK;
+      },
+      s);
 }
 
 int gdsp_fft2_device(const void *d_in, void *d_out, int64_t rows, int64_t cols, int inverse,

@@ -403,6 +403,47 @@ hipError_t launch_hilbert_mask(cd *spec, int64_t cnt, int64_t N, hipStream_t s);
 hipError_t launch_hilbert_store(int kind, const double *x, int64_t ldx, int64_t r0, int64_t cnt,
                                 int64_t n, int64_t N, const cd *spec, void *out, int64_t ldo,
                                 hipStream_t s);
+// Recursive filtering of real rows by S second-order sections (sosfilt.hip).
+// A launch filters the virtual row of io.n samples of every channel from the
+// states zi (channels x S x 2; NULL: zeros) and leaves the states after the
+// last sample in zf (NULL: not wanted). The virtual row (SosIo) is the row
+// itself, its odd extension by `pad` samples at both ends, or a row read from
+// its last sample backwards, of which only the last nout results are stored,
+// reversed back (sosfiltfilt's second pass).
+enum { SOS_IO_PLAIN = 0, SOS_IO_ODD_EXT = 1, SOS_IO_REVERSED = 2 };
+struct SosIo {
+  const double *src;  // rows of nx doubles, lds apart
+  int64_t lds;
+  double *dst;        // rows ldd apart: n results (nout where reversed)
+  int64_t ldd;
+  int64_t n;          // samples filtered: nx, nx + 2 pad, or <= nx where reversed
+  int64_t nx, pad, nout;
+  int mode;
+};
+constexpr int kSosThreads = 256, kSosE = 16, kSosTile = kSosThreads * kSosE;
+constexpr int kSosMaxFused = 8, kSosMaxSections = 64;
+// the time-parallel form's tables, built by the host (gdsp_api.hip): per
+// section a block of kSosSecDoubles — b0 b1 b2 a1 a2 at 0, the zero-input
+// response c[i][j] (output i of a thread for unit state j) at 8, M^(2^k), k <
+// 7, row-major 2 x 2 at 8 + 2 E, M = A^E the state map over a thread's samples
+// — then Phi = A^tile of the whole cascade, 2 S x 2 S row-major, at
+// kSosPhiOffset. The plain form takes b0 b1 b2 a1 a2 per section, 5 S doubles.
+constexpr int kSosSecDoubles = 72, kSosPhiOffset = kSosMaxFused * kSosSecDoubles;
+constexpr int kSosTableDoubles = kSosPhiOffset + 4 * kSosMaxFused * kSosMaxFused;
+constexpr int kSosTablePart = 448;
+struct SosTablePart {
+  int offset, count;
+  double v[kSosTablePart];
+};
+hipError_t launch_sos_tables(const double *host, int64_t count, double *tab, hipStream_t s);
+// scratch: channels (2 T + 1) 2 S doubles, T = ceil(n / tile) (pass 1's end
+// states and pass 2's entry states); not read where a row is one tile
+hipError_t launch_sos_tiles(const SosIo &io, const double *tab, int S, int64_t channels,
+                            const double *zi, double *zf, double *scratch, hipStream_t s);
+hipError_t launch_sos_plain(const SosIo &io, const double *coef, int S, int64_t channels,
+                            const double *zi, double *zf, hipStream_t s);
+hipError_t launch_sos_ffzi(const SosIo &io, int64_t at, const double *zi, int S, int64_t channels,
+                           double *zi_rows, hipStream_t s);
 // wav.ReadFloats conversion (wav.hip): audio_format 1 (bits 8 / 16) or 3
 hipError_t launch_wav_decode(const void *in, int64_t count, int audio_format, int bits,
                              void *out, bool f64, hipStream_t s);

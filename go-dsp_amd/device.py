@@ -239,6 +239,87 @@ def hilbert_batch(x, N=None, kind: str = "analytic", out=None, work=None, stream
     return out
 
 
+def _host_sos(sos):
+    import numpy as np
+    if _torch().is_tensor(sos):
+        sos = sos.detach().cpu().numpy()
+    s = np.ascontiguousarray(np.asarray(sos, dtype=np.float64))
+    assert s.ndim == 2 and s.shape[1] == 6, "sos must have the shape (S, 6)"
+    return s, s.ctypes.data_as(_lib._P)
+
+
+def sosfilt_batch(x, sos, zi=None, out=None, work=None, stream=None, return_zf: bool = False):
+    """fft.SosFiltBatch on a float64 CUDA tensor (channels, n; unit inner
+    stride, any row stride): every row through the sections sos ((S, 6), a host
+    array: the kernels' tables are host arithmetic) from the states zi
+    ((channels, S, 2) contiguous CUDA tensor; None: zeros) into out (same shape;
+    may be x itself, no other overlap). return_zf: also the final states as a
+    (channels, S, 2) tensor. work: float64 scratch of
+    gdsp_sosfilt_work_doubles(S, channels, n) elements; with it the call
+    neither allocates nor synchronises (gdsp_sosfilt_batch_device)."""
+    torch = _torch()
+    assert x.is_cuda and x.dtype == torch.float64 and x.dim() == 2
+    s, sp = _host_sos(sos)
+    S = s.shape[0]
+    channels, n = x.shape
+    if out is None:
+        out = torch.empty((channels, n), dtype=torch.float64, device=x.device)
+    assert out.is_cuda and out.dtype == torch.float64 and out.device == x.device
+    assert tuple(out.shape) == (channels, n)
+    assert n == 0 or (x.stride(1) == 1 and out.stride(1) == 1), "rows must have unit inner stride"
+    ldx = x.stride(0) if channels > 1 else n
+    ldo = out.stride(0) if channels > 1 else n
+    if zi is not None:
+        assert zi.is_cuda and zi.dtype == torch.float64 and zi.device == x.device
+        assert tuple(zi.shape) == (channels, S, 2) and zi.is_contiguous()
+    zf = torch.empty((channels, S, 2), dtype=torch.float64, device=x.device) if return_zf else None
+    if work is not None:
+        assert work.is_cuda and work.dtype == torch.float64 and work.is_contiguous()
+        assert work.numel() >= int(lib().gdsp_sosfilt_work_doubles(S, channels, n))
+    null = ctypes.c_void_p()
+    with torch.cuda.device(x.device):
+        check(lib().gdsp_sosfilt_batch_device(_ptr(x), ldx, sp, S,
+                                              _ptr(zi) if zi is not None else null, channels, n,
+                                              _ptr(out), ldo, _ptr(zf) if return_zf else null,
+                                              _ptr(work) if work is not None else null,
+                                              _stream_ptr(stream, x.device)),
+              "sosfilt_batch_device")
+    return (out, zf) if return_zf else out
+
+
+def sosfiltfilt_batch(x, sos, padlen=None, out=None, work=None, stream=None):
+    """fft.SosFiltFiltBatch on a float64 CUDA tensor (channels, n): zero-phase
+    filtering as scipy.signal.sosfiltfilt(sos, x, axis=1, padlen=padlen) into
+    out (same shape, no overlap with x). work: float64 scratch of
+    gdsp_sosfiltfilt_work_doubles(S, channels, n, padlen) elements, which holds
+    the forward pass's result (gdsp_sosfiltfilt_batch_device)."""
+    torch = _torch()
+    assert x.is_cuda and x.dtype == torch.float64 and x.dim() == 2
+    s, sp = _host_sos(sos)
+    S = s.shape[0]
+    channels, n = x.shape
+    pl = -1 if padlen is None else int(padlen)
+    assert padlen is None or pl >= 0
+    if out is None:
+        out = torch.empty((channels, n), dtype=torch.float64, device=x.device)
+    assert out.is_cuda and out.dtype == torch.float64 and out.device == x.device
+    assert tuple(out.shape) == (channels, n)
+    assert n == 0 or (x.stride(1) == 1 and out.stride(1) == 1), "rows must have unit inner stride"
+    ldx = x.stride(0) if channels > 1 else n
+    ldo = out.stride(0) if channels > 1 else n
+    if work is not None:
+        assert work.is_cuda and work.dtype == torch.float64 and work.is_contiguous()
+        p = pl if pl >= 0 else int(lib().gdsp_sosfiltfilt_padlen(sp, S))
+        assert work.numel() >= int(lib().gdsp_sosfiltfilt_work_doubles(S, channels, n, p))
+    with torch.cuda.device(x.device):
+        check(lib().gdsp_sosfiltfilt_batch_device(_ptr(x), ldx, sp, S, pl, channels, n, _ptr(out),
+                                                  ldo, _ptr(work) if work is not None
+                                                  else ctypes.c_void_p(),
+                                                  _stream_ptr(stream, x.device)),
+              "sosfiltfilt_batch_device")
+    return out
+
+
 def resample_poly_batch(x, up: int, down: int, taps=None, out=None, stream=None):
     """fft.ResamplePolyBatch on a float64 CUDA tensor (channels, n):
     scipy.signal.resample_poly(x, up, down, axis=1) with its default zero

@@ -252,6 +252,138 @@ def Envelope(x, N=None) -> np.ndarray:
     return EnvelopeBatch(np.asarray(x, dtype=np.float64).reshape(1, -1), N)[0]
 
 
+def _sos(sos, what: str) -> np.ndarray:
+    """Sections as a contiguous (S, 6) float64 array."""
+    if np.iscomplexobj(sos):
+        raise TypeError(f"{what}: complex coefficients are not supported")
+    s = np.ascontiguousarray(np.asarray(sos, dtype=np.float64))
+    if s.ndim != 2 or s.shape[1] != 6:
+        raise _lib.GDSPError(_lib.GDSP_ERR_INVALID, "sos must have the shape (S, 6)")
+    return s
+
+
+def sosfilt_fused(sos) -> bool:
+    """Whether SosFiltBatch runs these sections on the time-parallel kernel
+    under the current algorithm flags: 1 to 8 sections, each strictly inside
+    the stability triangle (gdsp_sosfilt_fused; host arithmetic)."""
+    s = _sos(sos, "sosfilt_fused")
+    return bool(lib().gdsp_sosfilt_fused(_p(s), s.shape[0]))
+
+
+def sosfilt_granule(S: int) -> int:
+    """G: a row cut at a multiple of G into calls chained by zi = zf gives the
+    bits of one call (gdsp_sosfilt_granule; host arithmetic)."""
+    return int(lib().gdsp_sosfilt_granule(int(S)))
+
+
+def sosfilt_zi(sos) -> np.ndarray:
+    """scipy.signal.sosfilt_zi(sos): the (S, 2) states of the settled unit step
+    response (gdsp_sosfilt_zi; host arithmetic in long double)."""
+    s = _sos(sos, "sosfilt_zi")
+    zi = np.empty((s.shape[0], 2), np.float64)
+    check(lib().gdsp_sosfilt_zi(_p(s), s.shape[0], _p(zi)), "sosfilt_zi")
+    return zi
+
+
+def sosfiltfilt_padlen(sos) -> int:
+    """scipy's default padlen of sosfiltfilt, 3 (2 S + 1 - min(#{b2 == 0},
+    #{a2 == 0})) (gdsp_sosfiltfilt_padlen)."""
+    s = _sos(sos, "sosfiltfilt_padlen")
+    return int(lib().gdsp_sosfiltfilt_padlen(_p(s), s.shape[0]))
+
+
+def butter_sos(order: int, Wn: float, btype: str = "low") -> np.ndarray:
+    """Butterworth low-pass or high-pass of the given order with its -3 dB edge
+    at Wn (1 = Nyquist), as (ceil(order / 2), 6) second-order sections, in
+    closed form: the analog poles w exp(i pi (2 k + order + 1) / (2 order)),
+    w = 2 tan(pi Wn / 2) the prewarped edge, each conjugate pair through the
+    bilinear transform s = 2 (z - 1) / (z + 1). An odd order gives a
+    first-order first section (b2 = a2 = 0); the pairs follow by increasing a2
+    (scipy's order). Every section has unit gain at DC (low) or at Nyquist
+    (high), where scipy.signal.butter(..., output="sos") puts the whole gain
+    into section 0: same denominators, same response."""
+    order = int(order)
+    if btype not in ("low", "high"):
+        raise ValueError("butter_sos: btype must be 'low' or 'high'")
+    if order < 1 or not (0.0 < float(Wn) < 1.0):
+        raise _lib.GDSPError(_lib.GDSP_ERR_INVALID, "order >= 1 and 0 < Wn < 1")
+    high = btype == "high"
+    w = 2.0 * np.tan(np.pi * float(Wn) / 2.0)
+    secs = []
+    if order % 2:
+        a0 = 2.0 + w
+        b = (2.0 / a0, -2.0 / a0, 0.0) if high else (w / a0, w / a0, 0.0)
+        secs.append([*b, 1.0, (w - 2.0) / a0, 0.0])
+    pairs = []
+    for k in range(order // 2):
+        c = -2.0 * np.cos(np.pi * (2 * k + order + 1) / (2 * order)) * w  # s^2 + c s + w^2
+        a0 = 4.0 + 2.0 * c + w * w
+        g = 4.0 / a0 if high else w * w / a0
+        pairs.append([g, (-2.0 if high else 2.0) * g, g, 1.0, (2.0 * w * w - 8.0) / a0,
+                      (4.0 - 2.0 * c + w * w) / a0])
+    pairs.sort(key=lambda q: q[5])
+    return np.array(secs + pairs, dtype=np.float64)
+
+
+def SosFiltBatch(rows, sos, zi=None, return_zf: bool = False):
+    """Additive recursive (IIR) filtering of every row of the real (channels,
+    n) array (or list of rows): scipy.signal.sosfilt(sos, rows, axis=1, zi=zi)
+    with one set of sections (S, 6) for all rows, a0 == 1. zi: (channels, S, 2)
+    initial states (None: zeros). return_zf: also the final states, so that a
+    recording can be filtered piece by piece (gdsp_sosfilt_batch)."""
+    x = _real_rows(rows, "SosFiltBatch")
+    s = _sos(sos, "SosFiltBatch")
+    channels, n = x.shape
+    S = s.shape[0]
+    x = np.ascontiguousarray(x)
+    z = None
+    if zi is not None:
+        z = np.ascontiguousarray(np.asarray(zi, dtype=np.float64))
+        if z.shape != (channels, S, 2):
+            raise _lib.GDSPError(_lib.GDSP_ERR_INVALID, "zi must have the shape (channels, S, 2)")
+    out = np.empty((channels, n), np.float64)
+    zf = np.zeros((channels, S, 2), np.float64) if return_zf else None
+    check(lib().gdsp_sosfilt_batch(_p(x), n, _p(s), S, _p(z) if z is not None else None, channels,
+                                   n, _p(out), n, _p(zf) if zf is not None else None),
+          "SosFiltBatch")
+    return (out, zf) if return_zf else out
+
+
+def SosFilt(x, sos, zi=None, return_zf: bool = False):
+    """scipy.signal.sosfilt(sos, x) of the real signal x (SosFiltBatch of one
+    row); zi and the returned zf are (S, 2)."""
+    if np.iscomplexobj(x):
+        raise TypeError("SosFilt: complex input is not supported")
+    z = None if zi is None else np.asarray(zi, dtype=np.float64)[None]
+    r = SosFiltBatch(np.asarray(x, dtype=np.float64).reshape(1, -1), sos, z, return_zf)
+    return (r[0][0], r[1][0]) if return_zf else r[0]
+
+
+def SosFiltFiltBatch(rows, sos, padlen=None) -> np.ndarray:
+    """Zero-phase filtering of every row: scipy.signal.sosfiltfilt(sos, rows,
+    axis=1, padtype="odd", padlen=padlen), forward and backward over the odd
+    extension of each row (padlen None: scipy's default, sosfiltfilt_padlen);
+    rows must be longer than padlen (gdsp_sosfiltfilt_batch)."""
+    x = np.ascontiguousarray(_real_rows(rows, "SosFiltFiltBatch"))
+    s = _sos(sos, "SosFiltFiltBatch")
+    channels, n = x.shape
+    pl = -1 if padlen is None else int(padlen)
+    if pl < 0 and padlen is not None:
+        raise _lib.GDSPError(_lib.GDSP_ERR_INVALID, "negative size")
+    out = np.empty((channels, n), np.float64)
+    check(lib().gdsp_sosfiltfilt_batch(_p(x), n, _p(s), s.shape[0], pl, channels, n, _p(out), n),
+          "SosFiltFiltBatch")
+    return out
+
+
+def SosFiltFilt(x, sos, padlen=None) -> np.ndarray:
+    """scipy.signal.sosfiltfilt(sos, x) of the real signal x (SosFiltFiltBatch
+    of one row)."""
+    if np.iscomplexobj(x):
+        raise TypeError("SosFiltFilt: complex input is not supported")
+    return SosFiltFiltBatch(np.asarray(x, dtype=np.float64).reshape(1, -1), sos, padlen)[0]
+
+
 def _rate_pair(up: int, down: int) -> tuple[int, int]:
     import math
     up, down = int(up), int(down)
@@ -469,6 +601,7 @@ ALGO_NO_FUSED_STFT = 1024
 ALGO_NO_FUSED_ISTFT = 4096  # 2048 is not a flag
 ALGO_NO_FUSED_UPFIRDN = 8192
 ALGO_NO_FUSED_HILBERT = 32768  # 16384 is not a flag
+ALGO_NO_FUSED_SOSFILT = 65536
 
 
 def SetAlgorithm(flags: int = ALGO_DEFAULT) -> None:

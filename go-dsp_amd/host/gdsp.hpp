@@ -277,6 +277,47 @@ inline std::vector<complex> ConvolveBatch(const std::vector<complex> &x,
   return r;
 }
 
+// Additive recursive filtering (scipy.signal.sosfilt): the x.size() / n rows
+// of x through the sections sos (6 per section: b0 b1 b2 1 a1 a2). zi, zf:
+// rows x S x 2 states (zi empty: zeros; zf NULL: not wanted).
+inline std::vector<double> SosFiltBatch(const std::vector<double> &x, size_t n,
+                                        const std::vector<double> &sos,
+                                        const std::vector<double> &zi = {},
+                                        std::vector<double> *zf = nullptr) {
+  if (n == 0 || x.size() % n != 0 || sos.size() % 6 != 0)
+    throw Panic(GDSP_ERR_UNEQUAL, "arrays not of equal size");
+  const int64_t rows = (int64_t)(x.size() / n), S = (int64_t)(sos.size() / 6);
+  if (!zi.empty() && zi.size() != (size_t)(rows * S * 2))
+    throw Panic(GDSP_ERR_UNEQUAL, "arrays not of equal size");
+  std::vector<double> r(x.size());
+  if (zf) zf->assign((size_t)(rows * S * 2), 0.0);
+  check(gdsp_sosfilt_batch(x.data(), (int64_t)n, sos.data(), S, zi.empty() ? nullptr : zi.data(),
+                           rows, (int64_t)n, r.data(), (int64_t)n, zf ? zf->data() : nullptr),
+        "SosFiltBatch");
+  return r;
+}
+
+// scipy.signal.sosfiltfilt with the odd extension (padlen -1: scipy's default)
+inline std::vector<double> SosFiltFiltBatch(const std::vector<double> &x, size_t n,
+                                            const std::vector<double> &sos,
+                                            long long padlen = -1) {
+  if (n == 0 || x.size() % n != 0 || sos.size() % 6 != 0)
+    throw Panic(GDSP_ERR_UNEQUAL, "arrays not of equal size");
+  std::vector<double> r(x.size());
+  check(gdsp_sosfiltfilt_batch(x.data(), (int64_t)n, sos.data(), (int64_t)(sos.size() / 6),
+                               (int64_t)padlen, (int64_t)(x.size() / n), (int64_t)n, r.data(),
+                               (int64_t)n),
+        "SosFiltFiltBatch");
+  return r;
+}
+
+// scipy.signal.sosfilt_zi: S x 2
+inline std::vector<double> SosFiltZi(const std::vector<double> &sos) {
+  std::vector<double> zi(sos.size() / 6 * 2);
+  check(gdsp_sosfilt_zi(sos.data(), (int64_t)(sos.size() / 6), zi.data()), "SosFiltZi");
+  return zi;
+}
+
 // fft.FFTN / IFFTN — fft.go:157-192
 inline dsputils::Matrix fftn(const dsputils::Matrix &m, int inverse) {
   std::vector<int64_t> d(m.dims.begin(), m.dims.end());

@@ -328,6 +328,28 @@ def EnvelopeChannels(w: Wav, frames: int, N=None):
     return device.hilbert_batch(x, nfft, kind="envelope").cpu().numpy()
 
 
+def IIRFilterChannels(w: Wav, frames: int, sos, zero_phase: bool = False):
+    """Every channel of a multi-channel file through a recursive filter: the
+    next `frames` frames of w, decoded planar on the GPU as for FilterChannels
+    and run through device.sosfilt_batch with the sections sos ((S, 6)), or
+    through device.sosfiltfilt_batch with zero_phase=True. Returns a
+    (NumChannels, frames) numpy array; row c equals fft.SosFiltBatch (or
+    SosFiltFiltBatch) of channel c's decoded samples."""
+    import torch
+
+    from . import device
+    C = int(w.NumChannels)
+    raw, _ = w._read_raw(frames * C)
+    if frames == 0:
+        raise _lib.Panic(_lib.GDSP_ERR_EMPTY, "empty input array")
+    dev = torch.device("cuda", torch.cuda.current_device())
+    rd = torch.frombuffer(bytearray(raw), dtype=torch.uint8).to(dev)
+    x = device_floats_planar(rd, frames, C, w.AudioFormat, w.BitsPerSample)
+    if zero_phase:
+        return device.sosfiltfilt_batch(x, sos).cpu().numpy()
+    return device.sosfilt_batch(x, sos, out=x).cpu().numpy()
+
+
 def ResampleChannels(w: Wav, frames: int, rate: int):
     """Every channel of a multi-channel file at the sample rate `rate`: the
     next `frames` frames of w, decoded planar on the GPU as for FilterChannels

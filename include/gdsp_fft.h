@@ -134,7 +134,12 @@ enum {
    * plan's inverse, a store kernel) also for the powers of 2 the fused
    * analytic-signal kernel serves. Read when the call is made. The bit 16384
    * is not used, like 2048: both stay unknown bits. */
-  GDSP_ALGO_NO_FUSED_HILBERT = 32768
+  GDSP_ALGO_NO_FUSED_HILBERT = 32768,
+  /* gdsp_sosfilt_batch, gdsp_sosfiltfilt_batch and their device entries on the
+   * plain form (one thread per row, sample by sample from global memory) also
+   * for the filters the time-parallel kernel serves; gdsp_sosfilt_fused then
+   * reports 0. Read when the call is made. */
+  GDSP_ALGO_NO_FUSED_SOSFILT = 65536
 };
 /* Unknown bits → GDSP_ERR_INVALID (the selection is left unchanged). */
 int gdsp_set_algorithm(unsigned flags);
@@ -200,7 +205,21 @@ unsigned gdsp_get_algorithm(void);
  *                             zeros gives exact zeros; a quiet row beside a
  *                             loud one keeps its own relative accuracy; rows
  *                             times 2^k give outputs times 2^k
- *                             (tests/test_hilbert_gpu.py) */
+ *                             (tests/test_hilbert_gpu.py)
+ *      recursive filters     (gdsp_sosfilt_batch, gdsp_sosfiltfilt_batch and
+ *                             their device entries, both forms) a row's outputs
+ *                             and final state depend on that row alone, bit for
+ *                             bit; x times 2^k (and zi times 2^k) gives y and zf
+ *                             times 2^k; a zero row with zero zi gives exact
+ *                             zeros. A bad x[c, j] makes every output i >= j of
+ *                             row c and its zf non-finite (sections whose a1, a2
+ *                             are not zero never forget it) and changes no bit of
+ *                             the outputs i < j, nor of any other row: every
+ *                             step of the scans takes from earlier samples
+ *                             only, by a select, never by a zero weight.
+ *                             sosfiltfilt: the whole row, and no other row.
+ *                             Stale out, work and zf buffers change nothing
+ *                             (tests/test_sosfilt_gpu.py) */
 
 /* ---- fft package: host pointers, synchronous ----------------------------- */
 
@@ -343,6 +362,83 @@ int gdsp_hilbert_batch(const double *x, int64_t ldx, int64_t rows, int64_t n, in
  * GDSP_ALGO_NO_FUSED_HILBERT), 0 where the composed form runs. Host arithmetic
  * only, no GPU needed. */
 int gdsp_hilbert_fused(int64_t nfft);
+
+/* Additive recursive (IIR) filtering of real rows by second-order sections (no
+ * reference equivalent; scipy.signal.sosfilt(sos, x, axis=1, zi=zi)): for
+ * `channels` rows of n float64, row c at x + c*ldx, and S sections sos[S][6] =
+ * (b0, b1, b2, a0, a1, a2) with a0 == 1, one set for all rows, every section
+ * is the transposed direct form II
+ *   y = b0*x + z0;   z0 = b1*x - a1*y + z1;   z1 = b2*x - a2*y,
+ * the sections applied in cascade order. zi[channels][S][2]: the states the
+ * rows start from (NULL: zeros); zf, same shape (NULL: not wanted): the states
+ * after the last sample, so that filtering [0, n1) and then [n1, n) with zi =
+ * zf is filtering [0, n). Strides in doubles.
+ * Two forms. Where gdsp_sosfilt_fused(sos, S) — 1 <= S <= 8, every section
+ * strictly inside the stability triangle |a2| < 1, |a1| < 1 + a2 — the
+ * time-parallel form: rows are cut into tiles of 4096 samples; pass 1 runs
+ * every tile from zero state and keeps its end state; pass 2 carries st[k+1] =
+ * Phi st[k] + g[k] along each row (Phi = A^4096 of the cascade, 2S x 2S, from
+ * the host in long double); pass 3 runs every tile from its true state and
+ * stores each sample once. Inside a tile a thread owns 16 samples and the
+ * threads' states are scanned through M^(2^k), M = A^16 of a section. A row of
+ * one tile runs pass 3 alone. Otherwise the plain form: one thread per row,
+ * sample by sample; any S <= 64 and any finite coefficients, unstable ones
+ * included. Both follow the recurrence above in fused multiply-adds; the
+ * time-parallel form differs from it by a small multiple of the recurrence's
+ * own roundoff.
+ * Cuts in time: G = gdsp_sosfilt_granule(S). A call on [0, k*G) followed by a
+ * call on [k*G, n) with zi = zf gives the bits of one call on [0, n); zf at
+ * such a cut is pass 2's value. The host entry cuts rows at multiples of G
+ * into chunks of at most 2^25 samples over all rows (SOSFILT_CHUNK_ELEMS), so
+ * host and device results are equal bit for bit. A cut elsewhere is equal
+ * within the accuracy of the form.
+ * In this order, before any device call: a negative size, or, with channels >
+ * 1, ldx < n or ldo < n -> GDSP_ERR_INVALID; channels == 0 -> GDSP_OK, nothing
+ * done; n == 0 or S == 0 -> GDSP_ERR_EMPTY; S > 64 -> GDSP_ERR_UNSUPPORTED; a
+ * NULL x, sos or out -> GDSP_ERR_INVALID; an a0 other than 1 or a coefficient
+ * that is not finite -> GDSP_ERR_INVALID. out may alias x: the caller's memory
+ * is only touched by host memcpy, chunk by chunk, each read before it is
+ * written. Runs on the current device. */
+int gdsp_sosfilt_batch(const double *x, int64_t ldx, const double *sos, int64_t S,
+                       const double *zi, int64_t channels, int64_t n, double *out, int64_t ldo,
+                       double *zf);
+/* 1 where the time-parallel kernel serves these sections under the current
+ * flags, 0 where the plain form runs (also for arguments the call refuses, and
+ * under GDSP_ALGO_NO_FUSED_SOSFILT). Host arithmetic, no GPU needed. */
+int gdsp_sosfilt_fused(const double *sos, int64_t S);
+/* G of the cuts above: 4096 for 1 <= S <= 64 (pass 2 is sequential over the
+ * tiles, so every tile boundary is a cut), 0 otherwise. Host arithmetic. */
+int64_t gdsp_sosfilt_granule(int64_t S);
+/* scipy.signal.sosfilt_zi(sos): zi[S][2], the states of the settled unit step
+ * response — per section, with g = (b0 + b1 + b2) / (1 + a1 + a2): z1 = b2 -
+ * a2 g, z0 = b1 - a1 g + z1, times the product of the earlier sections' g —
+ * in long double, rounded once. S < 0, a NULL pointer with S > 0, an a0 other
+ * than 1, a coefficient that is not finite or a section with 1 + a1 + a2 == 0
+ * -> GDSP_ERR_INVALID. Host arithmetic, no GPU needed. */
+int gdsp_sosfilt_zi(const double *sos, int64_t S, double *zi);
+/* Zero-phase filtering (scipy.signal.sosfiltfilt(sos, x, axis=1, padtype="odd",
+ * padlen=padlen)): every row is extended by padlen samples at both ends by odd
+ * reflection (2 x[0] - x[padlen - v] before, 2 x[n-1] - x[n-2-v] after),
+ * filtered forward from the state gdsp_sosfilt_zi times the extension's first
+ * sample, that result filtered backward from gdsp_sosfilt_zi times its last
+ * sample, and the middle n samples kept. padlen == -1: scipy's default,
+ * gdsp_sosfiltfilt_padlen. Both passes run gdsp_sosfilt_batch's forms; the
+ * extension is formed by the kernels' loader and never stored. The host entry
+ * cuts both passes in time at multiples of G and holds the intermediate, n + 2
+ * padlen doubles per row, in host memory; its results equal the device entry's
+ * bit for bit. gdsp_sosfilt_batch's checks in its order, padlen < -1 with the
+ * negative sizes; then n <= padlen, or a section with 1 + a1 + a2 == 0 ->
+ * GDSP_ERR_INVALID. */
+int gdsp_sosfiltfilt_batch(const double *x, int64_t ldx, const double *sos, int64_t S,
+                           int64_t padlen, int64_t channels, int64_t n, double *out,
+                           int64_t ldo);
+/* 3 * (2 S + 1 - min(#{b2 == 0}, #{a2 == 0})), scipy's default padlen; -1 for a
+ * NULL sos or S outside 1..64. Host arithmetic. */
+int64_t gdsp_sosfiltfilt_padlen(const double *sos, int64_t S);
+/* Doubles of d_work a device entry below takes (more than it uses where the
+ * plain form runs); -1 for sizes the calls refuse. Host arithmetic. */
+int64_t gdsp_sosfilt_work_doubles(int64_t S, int64_t channels, int64_t n);
+int64_t gdsp_sosfiltfilt_work_doubles(int64_t S, int64_t channels, int64_t n, int64_t padlen);
 
 /* Additive batched entry point (no reference equivalent): the
  * same transform as fft.FFT / fft.IFFT applied to `batch` contiguous rows of n
@@ -634,8 +730,9 @@ int gdsp_multi_stats(int64_t *batch_calls, int64_t *pwelch_calls, int64_t *rccl_
  * of their materialised form, the output ranges of gdsp_istft_batch and the
  * channel and segment runs of its materialised form, the composed FIR's
  * transform chunks, the output ranges of gdsp_upfirdn_batch, the row ranges
- * of gdsp_hilbert_batch and the row chunks of its composed form, and the
- * 65535-row pieces of gdsp_fft_axis_device / gdsp_fftn_device and of the
+ * of gdsp_hilbert_batch and the row chunks of its composed form, the time
+ * chunks of gdsp_sosfilt_batch and of both passes of gdsp_sosfiltfilt_batch,
+ * and the 65535-row pieces of gdsp_fft_axis_device / gdsp_fftn_device and of the
  * multi-pass, four-step and chirp-z executors).
  * multi_unit_launches: launches of a Pwelch, batched-Pwelch, Cpsd, STFT or ISTFT kernel
  * whose persistent workers each take at least two pairs (or pair groups). A
@@ -781,6 +878,24 @@ int gdsp_upfirdn_batch_device(const void *d_x, int64_t ldx, const void *d_h, int
  * where gdsp_hilbert_fused(N) (the fused call then neither allocates nor
  * synchronises); otherwise R * N * 24 bytes, R = min(rows, max(1, 2^24 div
  * N)): R rows of N complex128, then R rows of N float64, 16-byte aligned. */
+/* gdsp_sosfilt_batch and gdsp_sosfiltfilt_batch on device buffers (no
+ * reference equivalent), stream-ordered; sos is a host pointer (the tables are
+ * host arithmetic and reach the device as kernel arguments), d_zi and d_zf
+ * device pointers or NULL. d_out may be exactly d_x (same pointer and row
+ * stride) in gdsp_sosfilt_batch_device: pass 3 reads a tile before it stores
+ * it; any other overlap, and every overlap in gdsp_sosfiltfilt_batch_device ->
+ * GDSP_ERR_INVALID, decided after the host entry's checks. d_work (NULL: the
+ * library's workspace): gdsp_sosfilt_work_doubles or
+ * gdsp_sosfiltfilt_work_doubles float64 (the latter holds the forward pass's
+ * result, n + 2 padlen doubles per row); with it a call neither allocates nor
+ * synchronises. No row is cut: a call is bit-equal to the host entry's. */
+int gdsp_sosfilt_batch_device(const void *d_x, int64_t ldx, const double *sos, int64_t S,
+                              const void *d_zi, int64_t channels, int64_t n, void *d_out,
+                              int64_t ldo, void *d_zf, void *d_work, void *stream);
+int gdsp_sosfiltfilt_batch_device(const void *d_x, int64_t ldx, const double *sos, int64_t S,
+                                  int64_t padlen, int64_t channels, int64_t n, void *d_out,
+                                  int64_t ldo, void *d_work, void *stream);
+
 int gdsp_hilbert_batch_device(const void *d_x, int64_t ldx, int64_t rows, int64_t n,
                               int64_t nfft, int kind, void *d_out, int64_t ldo,
                               void *d_work, void *stream);
