@@ -81,6 +81,16 @@ SIGNATURES = {
     "gdsp_sosfiltfilt_padlen": (_I64, [_P, _I64]),
     "gdsp_sosfilt_work_doubles": (_I64, [_I64, _I64, _I64]),
     "gdsp_sosfiltfilt_work_doubles": (_I64, [_I64, _I64, _I64, _I64]),
+    "gdsp_czt_tables": (_I, [_I64, _I64, _I64, _D, _D, _D, _I64, _P, _P, _P]),
+    "gdsp_czt_length": (_I64, [_I64, _I64, ctypes.POINTER(_I)]),
+    "gdsp_czt_fused": (_I, [_I64, _I64]),
+    "gdsp_czt_batch": (_I, [_P, _I64, _I, _I64, _I64, _I64, _D, _D, _D, _I64, _P, _I64]),
+    "gdsp_czt_plan_create": (_I, [_I64, _I64, _D, _D, _D, _I64, ctypes.POINTER(_P)]),
+    "gdsp_czt_plan_destroy": (_I, [_P]),
+    "gdsp_czt_plan_info": (_I, [_P, ctypes.POINTER(_I64), ctypes.POINTER(_I64),
+                                ctypes.POINTER(_I64), ctypes.POINTER(_I)]),
+    "gdsp_czt_work_bytes": (_I64, [_P, _I64]),
+    "gdsp_czt_batch_device": (_I, [_P, _P, _I64, _I, _I64, _P, _I64, _P, _I64, _P]),
     "gdsp_fft_batch": (_I, [_P, _P, _I64, _I64, _I]),
     "gdsp_fft_real_batch": (_I, [_P, _P, _I64, _I64]),
     "gdsp_fft2": (_I, [_P, _P, _I64, _I64, _I]),

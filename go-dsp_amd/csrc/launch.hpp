@@ -444,6 +444,23 @@ hipError_t launch_sos_plain(const SosIo &io, const double *coef, int S, int64_t 
                             const double *zi, double *zf, hipStream_t s);
 hipError_t launch_sos_ffzi(const SosIo &io, int64_t at, const double *zi, int S, int64_t channels,
                            double *zi_rows, hipStream_t s);
+// The chirp-z transform of rows (czt.hip): row r of x (n float64 when `real`,
+// else complex128, ldx elements apart) times A, convolved on F = 2^log2f >= n
+// + m - 1 points with the chirp whose spectrum over F is vhat, times P; m
+// complex128 per row, ldo apart. A, vhat and P have F entries (A zero past n,
+// P zero past m). The fused kernel where czt_lds_applies(F), tw the KIND_LDS
+// plan's table; out must not overlap x. The composed form's kernels, rows [r0,
+// r0 + cnt): rows times A padded to F into buf, conj(spec vhat) in place, and
+// conj(spec) P stored.
+bool czt_lds_applies(int64_t F);
+hipError_t launch_czt_lds(int log2f, bool real, const void *x, int64_t ldx, int64_t rows,
+                          int64_t n, int64_t m, cd *out, int64_t ldo, const cd *tw, const cd *A,
+                          const cd *vhat, const cd *P, hipStream_t s);
+hipError_t launch_czt_pre(bool real, const void *x, int64_t ldx, int64_t r0, int64_t cnt,
+                          int64_t n, int64_t F, const cd *A, cd *buf, hipStream_t s);
+hipError_t launch_czt_mul(cd *spec, const cd *vhat, int64_t cnt, int64_t F, hipStream_t s);
+hipError_t launch_czt_post(const cd *spec, int64_t F, int64_t r0, int64_t cnt, int64_t m,
+                           const cd *P, cd *out, int64_t ldo, hipStream_t s);
 // wav.ReadFloats conversion (wav.hip): audio_format 1 (bits 8 / 16) or 3
 hipError_t launch_wav_decode(const void *in, int64_t count, int audio_format, int bits,
                              void *out, bool f64, hipStream_t s);

@@ -959,6 +959,15 @@ int get_plan(int64_t n, gdsp_plan **out, bool chirpz) {
   return get_plan_locked(dev, n, out, chirpz);
 }
 
+int device_table(int dev, const std::vector<cd> &h, DevPtr<cd> &out) {
+  return upload(dev, h.data(), h.size(), out);
+}
+
+int plan_spectrum_table(int dev, const gdsp_plan *fft, const std::vector<cd> &b, int64_t len,
+                        int64_t count, double scale, DevPtr<cd> &out) {
+  return spectrum_table(dev, fft, b, len, count, scale, out);
+}
+
 bool build_flags(unsigned *flags) {
   *flags = t_build_flags;
   return t_build_depth > 0;

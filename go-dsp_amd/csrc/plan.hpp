@@ -107,6 +107,15 @@ int get_plan(int64_t n, gdsp_plan **out, bool chirpz = false);
 // returns it during the build); false outside a build.
 bool build_flags(unsigned *flags);
 
+// What the planner's tables are made with, for a plan object kept outside the
+// cache (czt.hip): h as a complete device table; and FFT_len of each of the
+// `count` rows of b times scale, computed on the device by the engine itself
+// through the plan `fft` for len (the calling thread's stream is drained
+// before either returns). Neither takes the plan mutex itself.
+int device_table(int dev, const std::vector<gdsp::cd> &h, DevPtr<gdsp::cd> &out);
+int plan_spectrum_table(int dev, const gdsp_plan *fft, const std::vector<gdsp::cd> &b,
+                        int64_t len, int64_t count, double scale, DevPtr<gdsp::cd> &out);
+
 // The executors (gdsp_api.hip) as the planner uses them: a plan's table of
 // FFT_M(b) is computed by the engine itself, and a race times whole plans.
 int exec_plan(const gdsp_plan *p, const void *in, gdsp::cd *out, int64_t batch, bool inv,

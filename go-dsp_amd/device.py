@@ -239,6 +239,91 @@ def hilbert_batch(x, N=None, kind: str = "analytic", out=None, work=None, stream
     return out
 
 
+class CztPlan:
+    """A chirp-z plan on the current device (gdsp_czt_plan_create): X[k] =
+    sum_j x[j] z_k^-j on the m points z_k = a_abs exp(2 pi i (a_turns + k
+    step_turns / step_div)) for rows of n samples, as fft.CZTBatch (by default
+    m = n and the DFT's step). Owns the device tables; reusable across calls
+    and streams of its device. F: the convolution length; fused: whether a
+    call made now runs the fused kernel."""
+
+    def __init__(self, n: int, m=None, step_turns=None, step_div=None, a_turns: float = 0.0,
+                 a_abs: float = 1.0):
+        from .fft import _czt_step
+        self.n = int(n)
+        self.m, st, sd = _czt_step(self.n, m, step_turns, step_div)
+        self.handle = ctypes.c_void_p()
+        self.device = _torch().cuda.current_device()
+        check(lib().gdsp_czt_plan_create(self.n, self.m, float(a_abs), float(a_turns), st, sd,
+                                         ctypes.byref(self.handle)), "czt_plan_create")
+        v = [ctypes.c_int64() for _ in range(3)]
+        check(lib().gdsp_czt_plan_info(self.handle, *v, None), "czt_plan_info")
+        self.F = v[2].value
+
+    @property
+    def fused(self) -> bool:
+        f = ctypes.c_int()
+        check(lib().gdsp_czt_plan_info(self.handle, None, None, None, f), "czt_plan_info")
+        return bool(f.value)
+
+    def work_bytes(self, rows: int) -> int:
+        """Bytes of `work` czt_batch takes for `rows` rows under the current
+        flags (0 in the fused form)."""
+        return int(lib().gdsp_czt_work_bytes(self.handle, int(rows)))
+
+    def __del__(self):
+        h, self.handle = getattr(self, "handle", None), None
+        if h:
+            try:
+                lib().gdsp_czt_plan_destroy(h)
+            except Exception:
+                pass
+
+
+def czt_batch(x, plan: CztPlan, out=None, work=None, stream=None):
+    """fft.CZTBatch on a float64 or complex128 CUDA tensor (rows, n; unit
+    inner stride, any row stride) through a CztPlan: m complex128 per row into
+    out (rows, m; unit inner stride, any row stride), which must not overlap x
+    and is allocated only when not given. work: scratch (any dtype) of
+    plan.work_bytes(rows) bytes for the composed form; the fused form takes
+    none, and with work given a call neither allocates nor synchronises."""
+    torch = _torch()
+    assert x.is_cuda and x.dim() == 2 and x.dtype in (torch.float64, torch.complex128)
+    rows, n = x.shape
+    assert n == plan.n and x.device.index == plan.device
+    if out is None:
+        out = torch.empty((rows, plan.m), dtype=torch.complex128, device=x.device)
+    assert out.is_cuda and out.dtype == torch.complex128 and out.device == x.device
+    assert tuple(out.shape) == (rows, plan.m)
+    assert x.stride(1) == 1 and out.stride(1) == 1, "rows must have unit inner stride"
+    ldx = x.stride(0) if rows > 1 else n
+    ldo = out.stride(0) if rows > 1 else plan.m
+    wp, wb = ctypes.c_void_p(), 0
+    if work is not None:
+        assert work.is_cuda and work.device == x.device and work.is_contiguous()
+        wp, wb = _ptr(work), work.numel() * work.element_size()
+    with torch.cuda.device(x.device):
+        check(lib().gdsp_czt_batch_device(plan.handle, _ptr(x), ldx, int(x.dtype == torch.float64),
+                                          rows, _ptr(out), ldo, wp, wb,
+                                          _stream_ptr(stream, x.device)), "czt_batch_device")
+    return out
+
+
+def zoom_fft_batch(x, fn, m=None, fs: float = 2, endpoint: bool = False, out=None):
+    """fft.ZoomFFTBatch on a CUDA tensor (rows, n): the spectrum of every row
+    at m frequencies from f1 to f2 (scipy.signal.zoom_fft), through a CztPlan
+    built for the call."""
+    from .fft import _zoom_params
+    torch = _torch()
+    m = x.shape[1] if m is None else int(m)
+    _, _, at, st, sd = _zoom_params(fn, m, fs, endpoint)
+    with torch.cuda.device(x.device):
+        p = CztPlan(x.shape[1], m, st, sd, at)
+        out = czt_batch(x, p, out=out)
+        torch.cuda.current_stream(x.device).synchronize()  # before the plan's tables go
+    return out
+
+
 def _host_sos(sos):
     import numpy as np
     if _torch().is_tensor(sos):

@@ -262,6 +262,113 @@ def _sos(sos, what: str) -> np.ndarray:
     return s
 
 
+def czt_length(n: int, m: int) -> tuple[int, bool]:
+    """(F, fused): the convolution length CZTBatch uses for n samples and m
+    points (0 where n + m - 1 exceeds 2^20: the call would fail) and whether
+    the fused chirp-z kernel runs it under the current algorithm flags
+    (gdsp_czt_length; host arithmetic)."""
+    fused = _lib._I(0)
+    f = int(lib().gdsp_czt_length(int(n), int(m), fused))
+    return f, bool(fused.value)
+
+
+def czt_fused(n: int, m: int) -> bool:
+    """Whether CZTBatch runs (n, m) on the fused chirp-z kernel under the
+    current algorithm flags (gdsp_czt_fused; host arithmetic)."""
+    return bool(lib().gdsp_czt_fused(int(n), int(m)))
+
+
+def _czt_step(n: int, m, step_turns, step_div):
+    m = int(n) if m is None else int(m)
+    if step_turns is None and step_div is None:
+        return m, 1.0, max(m, 1)  # the DFT grid of m points
+    return m, float(1.0 if step_turns is None else step_turns), int(1 if step_div is None else step_div)
+
+
+def czt_points(m: int, step_turns=None, step_div=None, a_turns: float = 0.0,
+               a_abs: float = 1.0) -> np.ndarray:
+    """The m points z_k = a_abs exp(2 pi i (a_turns + k step_turns / step_div))
+    CZT evaluates on (scipy.signal.czt_points with w = exp(-2 pi i step), a =
+    a_abs exp(2 pi i a_turns)); by default the DFT's. Host arithmetic in
+    float64, for plotting: the transform itself takes every angle exactly."""
+    m, st, sd = _czt_step(m, m, step_turns, step_div)
+    k = np.arange(m, dtype=np.float64)
+    return float(a_abs) * np.exp(2j * np.pi * (float(a_turns) + k * st / sd))
+
+
+def CZTBatch(rows, m=None, step_turns=None, step_div=None, a_turns: float = 0.0,
+             a_abs: float = 1.0) -> np.ndarray:
+    """Additive chirp-z transform of every row of the real or complex (rows,
+    n) array on m points of a circle: X[k] = sum_j x[j] z_k^-j with z_k = a_abs
+    exp(2 pi i (a_turns + k step_turns / step_div)), angles in turns, the step
+    the exact rational step_turns / step_div (an int64 divisor). By default m =
+    n and the step is 1 / m: the DFT. scipy.signal.czt(rows, m, w, a, axis=1)
+    with w = exp(-2 pi i step), a = a_abs exp(2 pi i a_turns); spirals (|w| !=
+    1) are not offered. complex128 (rows, m). Real rows stay real on the way
+    to the GPU."""
+    x = np.asarray(rows)
+    if x.ndim != 2:
+        raise ValueError("CZTBatch expects a 2-D (rows, n) array")
+    real = not np.iscomplexobj(x)
+    x = np.ascontiguousarray(x, dtype=np.float64 if real else np.complex128)
+    r, n = x.shape
+    m, st, sd = _czt_step(n, m, step_turns, step_div)
+    if m < 0:
+        raise _lib.GDSPError(_lib.GDSP_ERR_INVALID, "negative size")
+    out = np.empty((r, m), np.complex128)
+    check(lib().gdsp_czt_batch(_p(x), n, int(real), r, n, m, float(a_abs), float(a_turns), st, sd,
+                               _p(out), m), "CZTBatch")
+    return out
+
+
+def CZT(x, m=None, step_turns=None, step_div=None, a_turns: float = 0.0,
+        a_abs: float = 1.0) -> np.ndarray:
+    """scipy.signal.czt of the signal x on an arc of a circle (CZTBatch of one
+    row); by default its DFT."""
+    x = np.asarray(x).reshape(1, -1)
+    return CZTBatch(x, m, step_turns, step_div, a_turns, a_abs)[0]
+
+
+def _zoom_params(fn, m: int, fs: float, endpoint: bool):
+    f = np.atleast_1d(np.asarray(fn, dtype=np.float64))
+    if f.size == 1:
+        f1, f2 = 0.0, float(f[0])
+    elif f.size == 2:
+        f1, f2 = float(f[0]), float(f[1])
+    else:
+        raise ValueError("fn must be a scalar or a pair")
+    m = int(m)
+    div = m - 1 if endpoint else m
+    return f1, f2, f1 / fs, (f2 - f1) / fs, max(div, 1)
+
+
+def zoom_freqs(fn, m: int, fs: float = 2, endpoint: bool = False) -> np.ndarray:
+    """The m frequencies ZoomFFT(x, fn, m, fs, endpoint) evaluates:
+    numpy.linspace(f1, f2, m, endpoint=endpoint)."""
+    f1, f2, _, _, _ = _zoom_params(fn, m, fs, endpoint)
+    return np.linspace(f1, f2, int(m), endpoint=bool(endpoint))
+
+
+def ZoomFFTBatch(rows, fn, m=None, fs: float = 2, endpoint: bool = False) -> np.ndarray:
+    """scipy.signal.zoom_fft(rows, fn, m, fs=fs, endpoint=endpoint, axis=1):
+    the spectrum of every row at m frequencies from f1 to f2 (fn = [f1, f2],
+    or a scalar f2 with f1 = 0), at the sampling rate fs. CZTBatch with a_turns
+    = f1 / fs and the exact step ((f2 - f1) / fs) / m (or m - 1 with
+    endpoint)."""
+    x = np.asarray(rows)
+    if x.ndim != 2:
+        raise ValueError("ZoomFFTBatch expects a 2-D (rows, n) array")
+    m = x.shape[1] if m is None else int(m)
+    _, _, at, st, sd = _zoom_params(fn, m, fs, endpoint)
+    return CZTBatch(x, m, st, sd, at)
+
+
+def ZoomFFT(x, fn, m=None, fs: float = 2, endpoint: bool = False) -> np.ndarray:
+    """scipy.signal.zoom_fft(x, fn, m, fs=fs, endpoint=endpoint) of one signal
+    (ZoomFFTBatch of one row)."""
+    return ZoomFFTBatch(np.asarray(x).reshape(1, -1), fn, m, fs, endpoint)[0]
+
+
 def sosfilt_fused(sos) -> bool:
     """Whether SosFiltBatch runs these sections on the time-parallel kernel
     under the current algorithm flags: 1 to 8 sections, each strictly inside
@@ -602,6 +709,7 @@ ALGO_NO_FUSED_ISTFT = 4096  # 2048 is not a flag
 ALGO_NO_FUSED_UPFIRDN = 8192
 ALGO_NO_FUSED_HILBERT = 32768  # 16384 is not a flag
 ALGO_NO_FUSED_SOSFILT = 65536
+ALGO_NO_FUSED_CZT = 262144  # 131072 is not a flag
 
 
 def SetAlgorithm(flags: int = ALGO_DEFAULT) -> None:

@@ -350,6 +350,27 @@ def IIRFilterChannels(w: Wav, frames: int, sos, zero_phase: bool = False):
     return device.sosfilt_batch(x, sos, out=x).cpu().numpy()
 
 
+def ZoomChannels(w: Wav, frames: int, fn, m=None, endpoint: bool = False):
+    """The zoomed spectrum of every channel of a multi-channel file: the next
+    `frames` frames of w, decoded planar on the GPU as for FilterChannels and
+    run through device.zoom_fft_batch at m frequencies (None: frames) from f1
+    to f2 Hz (fn = [f1, f2] or f2), at the file's sample rate. Returns a
+    (NumChannels, m) complex128 numpy array; row c equals fft.ZoomFFTBatch of
+    channel c's decoded samples."""
+    import torch
+
+    from . import device
+    C = int(w.NumChannels)
+    raw, _ = w._read_raw(frames * C)
+    mm = frames if m is None else int(m)
+    if frames == 0 or mm == 0:
+        raise _lib.Panic(_lib.GDSP_ERR_EMPTY, "empty input array")
+    dev = torch.device("cuda", torch.cuda.current_device())
+    rd = torch.frombuffer(bytearray(raw), dtype=torch.uint8).to(dev)
+    x = device_floats_planar(rd, frames, C, w.AudioFormat, w.BitsPerSample)
+    return device.zoom_fft_batch(x, fn, mm, float(w.SampleRate), endpoint).cpu().numpy()
+
+
 def ResampleChannels(w: Wav, frames: int, rate: int):
     """Every channel of a multi-channel file at the sample rate `rate`: the
     next `frames` frames of w, decoded planar on the GPU as for FilterChannels

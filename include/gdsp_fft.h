@@ -139,7 +139,14 @@ enum {
    * plain form (one thread per row, sample by sample from global memory) also
    * for the filters the time-parallel kernel serves; gdsp_sosfilt_fused then
    * reports 0. Read when the call is made. */
-  GDSP_ALGO_NO_FUSED_SOSFILT = 65536
+  GDSP_ALGO_NO_FUSED_SOSFILT = 65536,
+  /* gdsp_czt_batch / gdsp_czt_batch_device on the composed form (a
+   * premultiply-and-pad kernel, the plan's transform, the product with the
+   * chirp's spectrum, the plan's transform again, a postmultiply-and-store
+   * kernel) also for the convolution lengths the fused chirp-z kernel serves;
+   * gdsp_czt_fused then reports 0. Read when the call is made. The bit 131072
+   * is not used, like 2048 and 16384: all three stay unknown bits. */
+  GDSP_ALGO_NO_FUSED_CZT = 262144
 };
 /* Unknown bits → GDSP_ERR_INVALID (the selection is left unchanged). */
 int gdsp_set_algorithm(unsigned flags);
@@ -219,7 +226,16 @@ unsigned gdsp_get_algorithm(void);
  *                             only, by a select, never by a zero weight.
  *                             sosfiltfilt: the whole row, and no other row.
  *                             Stale out, work and zf buffers change nothing
- *                             (tests/test_sosfilt_gpu.py) */
+ *                             (tests/test_sosfilt_gpu.py)
+ *      CZT                   (gdsp_czt_batch, gdsp_czt_batch_device, both forms)
+ *                             a row depends on itself alone, bit for bit,
+ *                             whatever its neighbours hold and however a job
+ *                             is cut into calls, and a zero row gives zeros. A
+ *                             NaN or Inf in a row makes all m outputs of that
+ *                             row non-finite, in both parts, and changes no bit
+ *                             elsewhere; rows times 2^k give outputs times 2^k
+ *                             (the inverse's 1 / F is a power of 2, folded into
+ *                             the chirp's spectrum) (tests/test_czt_gpu.py) */
 
 /* ---- fft package: host pointers, synchronous ----------------------------- */
 
@@ -439,6 +455,65 @@ int64_t gdsp_sosfiltfilt_padlen(const double *sos, int64_t S);
  * plain form runs); -1 for sizes the calls refuse. Host arithmetic. */
 int64_t gdsp_sosfilt_work_doubles(int64_t S, int64_t channels, int64_t n);
 int64_t gdsp_sosfiltfilt_work_doubles(int64_t S, int64_t channels, int64_t n, int64_t padlen);
+
+/* The chirp-z transform of rows on an arc of a circle (no reference
+ * equivalent; scipy.signal.czt with |w| = 1 and scipy.signal.zoom_fft): the
+ * z-transform of every row on m points
+ *   z_k  = a_abs * exp(2 pi i (a_turns + k * step)),  step = step_turns / step_div
+ *   X[k] = sum_{j<n} x[j] * z_k^(-j),                 k = 0 ... m-1
+ * (angles in turns; scipy's w = exp(-2 pi i step), a = a_abs exp(2 pi i
+ * a_turns)). The step is the rational number step_turns / step_div taken
+ * EXACTLY, not the rounded quotient: step_turns = 1, step_div = m = n is the
+ * DFT itself, and zoom_fft(fn = [f1, f2], m, fs, endpoint) is a_turns = f1 /
+ * fs, step_turns = (f2 - f1) / fs, step_div = m (m - 1 with endpoint). X[k]
+ * moves by about 2 pi n m d for an error d in the step, which is why the ABI
+ * takes reals and a divisor and no complex w. a_abs != 1 is a circle of
+ * another radius (rows damped by a_abs^-j); a_abs^-(n-1) must stay inside the
+ * normal double range. Spirals (|w| != 1) are NOT offered: Bluestein's split of
+ * |w|^(jk) into |w|^(+-j^2/2) makes the convolution's error relative to the
+ * largest of those factors (6e16 u at n = m = 1000 with a chirp range of
+ * e^+-40, in scipy as well), and the engine does not offer what it cannot
+ * compute.
+ * With c(j) = exp(-pi i step j^2) and F = gdsp_czt_length(n, m):
+ *   A[j] = a_abs^-j exp(-2 pi i j a_turns) c(j), j < n;  P[k] = c(k), k < m
+ *   v[d mod F] = conj(c(d)), -(n-1) <= d <= m-1, zero elsewhere
+ *   X[k] = P[k] IFFT_F(FFT_F(x A, zero-padded) FFT_F(v))[k]
+ * Every angle (j^2 step_turns / (2 step_div) and j a_turns turns, modulo 1) is
+ * reduced exactly in integers on the parameters' significands before any
+ * floating-point trigonometry; sine, cosine and a_abs^-j are then taken in long
+ * double and rounded once.
+ *
+ * gdsp_czt_tables: A (n), v (F) and P (m) complex128 for any F >= n + m - 1, F
+ * <= 2^20. Host arithmetic, no GPU needed. n < 1, m < 1, F out of range, a NULL
+ * pointer, a_abs <= 0, a parameter that is not finite, step_div < 1, or an
+ * entry of A whose modulus is not finite and normal -> GDSP_ERR_INVALID. */
+int gdsp_czt_tables(int64_t n, int64_t m, int64_t F, double a_abs, double a_turns,
+                    double step_turns, int64_t step_div, double *A, double *v, double *P);
+/* The convolution length F = max(256, the next power of 2 >= n + m - 1), or 0
+ * where it would exceed 2^20 (or n < 1 or m < 1): the entries then return
+ * GDSP_ERR_UNSUPPORTED. *fused (may be NULL): 1 where F <= 16384 and
+ * GDSP_ALGO_NO_FUSED_CZT is clear. Host arithmetic. */
+int64_t gdsp_czt_length(int64_t n, int64_t m, int *fused);
+/* 1 where the fused chirp-z kernel serves (n, m) under the current flags, 0
+ * where the composed form runs or nothing does. Host arithmetic. */
+int gdsp_czt_fused(int64_t n, int64_t m);
+/* gdsp_czt_batch: `rows` rows of n float64 (is_real = 1) or complex128
+ * (is_real = 0), row r at x + r*ldx elements, m complex128 per row to out +
+ * r*ldo complex128. Host pointers, synchronous; builds and frees its plan.
+ * Where gdsp_czt_fused(n, m), one kernel per range: a row times A as it is
+ * loaded, FFT_F, times FFT_F(v) / F, the second FFT_F as the inverse with P on
+ * its last pass, m outputs stored; otherwise the composed form in chunks of at
+ * most 2^24 / F rows. Host jobs are cut into ranges of at most 2^24 / F rows; a
+ * row's bits do not depend on the range it falls in.
+ * In this order, before any device call: a negative size, is_real outside 0..1,
+ * with rows > 1 ldx < n or ldo < m, a_abs <= 0, a parameter that is not finite
+ * or step_div < 1 -> GDSP_ERR_INVALID; rows == 0 -> GDSP_OK, nothing done; n ==
+ * 0 or m == 0 -> GDSP_ERR_EMPTY; a NULL pointer -> GDSP_ERR_INVALID; n + m - 1 >
+ * 2^20 -> GDSP_ERR_UNSUPPORTED; a_abs^-(n-1) outside the normal range ->
+ * GDSP_ERR_INVALID. Runs on the current device. */
+int gdsp_czt_batch(const void *x, int64_t ldx, int is_real, int64_t rows, int64_t n, int64_t m,
+                   double a_abs, double a_turns, double step_turns, int64_t step_div, double *out,
+                   int64_t ldo);
 
 /* Additive batched entry point (no reference equivalent): the
  * same transform as fft.FFT / fft.IFFT applied to `batch` contiguous rows of n
@@ -732,6 +807,7 @@ int gdsp_multi_stats(int64_t *batch_calls, int64_t *pwelch_calls, int64_t *rccl_
  * transform chunks, the output ranges of gdsp_upfirdn_batch, the row ranges
  * of gdsp_hilbert_batch and the row chunks of its composed form, the time
  * chunks of gdsp_sosfilt_batch and of both passes of gdsp_sosfiltfilt_batch,
+ * the row ranges of gdsp_czt_batch and the row chunks of its composed form,
  * and the 65535-row pieces of gdsp_fft_axis_device / gdsp_fftn_device and of the
  * multi-pass, four-step and chirp-z executors).
  * multi_unit_launches: launches of a Pwelch, batched-Pwelch, Cpsd, STFT or ISTFT kernel
@@ -899,6 +975,39 @@ int gdsp_sosfiltfilt_batch_device(const void *d_x, int64_t ldx, const double *so
 int gdsp_hilbert_batch_device(const void *d_x, int64_t ldx, int64_t rows, int64_t n,
                               int64_t nfft, int kind, void *d_out, int64_t ldo,
                               void *d_work, void *stream);
+
+/* The chirp-z transform's plan (gdsp_czt_batch's parameters, no reference
+ * equivalent): the device tables A, FFT_F(v) / F (computed from the float64 v
+ * by the engine's own transform) and P on the caller's current device, and the
+ * plan cache's F-point transform. In this order: a NULL plan pointer, a
+ * negative size, a_abs <= 0, a parameter that is not finite or step_div < 1 ->
+ * GDSP_ERR_INVALID; n == 0 or m == 0 -> GDSP_ERR_EMPTY; n + m - 1 > 2^20 ->
+ * GDSP_ERR_UNSUPPORTED; a_abs^-(n-1) outside the normal double range ->
+ * GDSP_ERR_INVALID; then the device. A plan may be used by any number of
+ * calls and streams of its device; gdsp_czt_plan_destroy waits for the device
+ * and frees the tables (NULL: nothing). gdsp_czt_plan_info: n, m, F and
+ * whether a call made now runs the fused kernel (any pointer may be NULL). */
+typedef struct gdsp_czt_plan gdsp_czt_plan;
+int gdsp_czt_plan_create(int64_t n, int64_t m, double a_abs, double a_turns, double step_turns,
+                         int64_t step_div, gdsp_czt_plan **plan);
+int gdsp_czt_plan_destroy(gdsp_czt_plan *plan);
+int gdsp_czt_plan_info(const gdsp_czt_plan *plan, int64_t *n, int64_t *m, int64_t *F,
+                       int *fused);
+/* Bytes of d_work for `rows` rows under the current flags: 0 in the fused
+ * form, else min(rows, max(1, 2^24 div F)) * F * 16. Host arithmetic. */
+int64_t gdsp_czt_work_bytes(const gdsp_czt_plan *plan, int64_t rows);
+/* gdsp_czt_batch on device buffers, stream-ordered: d_x rows of n float64
+ * (is_real = 1) or complex128 (0) at stride ldx elements, d_out rows of m
+ * complex128 at stride ldo. In this order: a NULL plan, a negative rows,
+ * is_real outside 0..1, with rows > 1 ldx < n or ldo < m -> GDSP_ERR_INVALID;
+ * rows == 0 -> GDSP_OK; a NULL d_x or d_out -> GDSP_ERR_INVALID; overlapping
+ * address ranges of d_x and d_out, or a d_work of fewer than
+ * gdsp_czt_work_bytes(plan, rows) bytes (work_bytes) -> GDSP_ERR_INVALID.
+ * d_work may be NULL (the library's workspace pool); the fused form takes
+ * none, and with d_work given a call neither allocates nor synchronises. */
+int gdsp_czt_batch_device(const gdsp_czt_plan *plan, const void *d_x, int64_t ldx, int is_real,
+                          int64_t rows, void *d_out, int64_t ldo, void *d_work,
+                          int64_t work_bytes, void *stream);
 
 /* FFT2/IFFT2 on a device rows×cols complex128 matrix. d_work: scratch of
  * rows*cols complex128 (may be NULL: the library allocates stream-ordered). */
