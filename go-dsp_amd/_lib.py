@@ -37,6 +37,11 @@ GDSP_HILBERT_ANALYTIC = 0
 GDSP_HILBERT_QUADRATURE = 1
 GDSP_HILBERT_ENVELOPE = 2
 
+# the norm of gdsp_dct_batch
+GDSP_DCT_BACKWARD = 0
+GDSP_DCT_ORTHO = 1
+GDSP_DCT_FORWARD = 2
+
 _P = ctypes.c_void_p
 _I64 = ctypes.c_int64
 _I = ctypes.c_int
@@ -91,6 +96,11 @@ SIGNATURES = {
                                 ctypes.POINTER(_I64), ctypes.POINTER(_I)]),
     "gdsp_czt_work_bytes": (_I64, [_P, _I64]),
     "gdsp_czt_batch_device": (_I, [_P, _P, _I64, _I, _I64, _P, _I64, _P, _I64, _P]),
+    "gdsp_dct_batch": (_I, [_P, _I64, _I64, _I64, _I64, _I, _I, _P, _I64]),
+    "gdsp_dct_batch_device": (_I, [_P, _I64, _I64, _I64, _I64, _I, _I, _P, _I64, _P, _P]),
+    "gdsp_dct_fused": (_I, [_I64]),
+    "gdsp_dct_work_doubles": (_I64, [_I64, _I64]),
+    "gdsp_dct_twiddles": (_I, [_I64, _P]),
     "gdsp_fft_batch": (_I, [_P, _P, _I64, _I64, _I]),
     "gdsp_fft_real_batch": (_I, [_P, _P, _I64, _I64]),
     "gdsp_fft2": (_I, [_P, _P, _I64, _I64, _I]),

@@ -1,7 +1,8 @@
 // api_internal.hpp — the host vocabulary the translation units of the C ABI
 // share: gdsp_api.hip (streams, staging, workspaces, executors, the FFT,
 // Convolve, FIR, resampling, Hilbert and recursive-filter entries), czt.hip (the chirp-z
-// transform's tables, plan object and entries), welch.hip (the Welch family: Pwelch, batched
+// transform's tables, plan object and entries), dct.hip (the cosine transforms' table and
+// entries), welch.hip (the Welch family: Pwelch, batched
 // Pwelch, Cpsd, STFT, ISTFT), plan.hip (the planner) and multi.hip (the multi-device
 // layer). Not part of the C ABI.
 #pragma once
@@ -50,7 +51,7 @@ enum Slot {
   SLOT_FS3, SLOT_FFTN, SLOT_MX0, SLOT_MX1, SLOT_PARTS, SLOT_CONV, SLOT_CP_Y, SLOT_CP_OUT, SLOT_CP_BAL,
   SLOT_FIR, SLOT_FIR_H, SLOT_FIR_OUT, SLOT_ST_ROWS, SLOT_ST_OUT, SLOT_IS_D,
   SLOT_UF, SLOT_UF_H, SLOT_UF_OUT, SLOT_HB, SLOT_HB_OUT,
-  SLOT_SOS, SLOT_SOS_Z, SLOT_CZT, SLOT_CZT_OUT,
+  SLOT_SOS, SLOT_SOS_Z, SLOT_CZT, SLOT_CZT_OUT, SLOT_DCT, SLOT_DCT_OUT,
   SLOT_COUNT
 };
 

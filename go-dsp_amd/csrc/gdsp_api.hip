@@ -84,7 +84,8 @@ constexpr unsigned kAlgoAll = GDSP_ALGO_GENERIC_MIXED | GDSP_ALGO_NO_CHIRPZ_PART
                               GDSP_ALGO_NO_FUSED_CPSD | GDSP_ALGO_NO_FUSED_FIR |
                               GDSP_ALGO_NO_FUSED_STFT | GDSP_ALGO_NO_FUSED_ISTFT |
                               GDSP_ALGO_NO_FUSED_UPFIRDN | GDSP_ALGO_NO_FUSED_HILBERT |
-                              GDSP_ALGO_NO_FUSED_SOSFILT | GDSP_ALGO_NO_FUSED_CZT;
+                              GDSP_ALGO_NO_FUSED_SOSFILT | GDSP_ALGO_NO_FUSED_CZT |
+                              GDSP_ALGO_NO_FUSED_DCT;
 
 // Scratch device memory: a grow-only buffer per (device, stream, use-site
 // slot), allocated with hipMalloc. Reuse is ordered by the stream itself: a

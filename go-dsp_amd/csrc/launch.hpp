@@ -403,6 +403,31 @@ hipError_t launch_hilbert_mask(cd *spec, int64_t cnt, int64_t N, hipStream_t s);
 hipError_t launch_hilbert_store(int kind, const double *x, int64_t ldx, int64_t r0, int64_t cnt,
                                 int64_t n, int64_t N, const cd *spec, void *out, int64_t ldo,
                                 hipStream_t s);
+// The cosine transforms of real rows (dct.hip): row r of x (n samples, ldx
+// apart) cut or zero-padded to N, type 2 or 3, N float64 per row, ldo apart.
+// wk: w_k = exp(-i pi k / (2N)), N entries. Type 2 stores Re(w_k V[k]) scale
+// (k = 0: scale0); type 3 takes x[0] a0 and stores v scale. The fused kernel:
+// N = 2^log2n where dct_lds_applies(N), one row per transform, tw the KIND_LDS
+// plan's table; out may be exactly x (same stride, N <= n), nothing else of
+// it. The composed form's kernels for any N, rows [r0, r0 + cnt): type 2's
+// permuted padded rows into buf and its store from the full spectra; type 3's
+// rows of conj W into spec and its store from the transform's real parts;
+// N = 1: out[r ldo] = x[r ldx] c.
+bool dct_lds_applies(int64_t N);
+hipError_t launch_dct_lds(int log2n, int type, const double *x, int64_t ldx, int64_t rows,
+                          int64_t n, double *out, int64_t ldo, const cd *tw, const cd *wk,
+                          double a0, double scale, double scale0, hipStream_t s);
+hipError_t launch_dct2_gather(const double *x, int64_t ldx, int64_t r0, int64_t cnt, int64_t n,
+                              int64_t N, double *buf, hipStream_t s);
+hipError_t launch_dct2_store(const cd *spec, const cd *wk, int64_t N, int64_t r0, int64_t cnt,
+                             double *out, int64_t ldo, double scale, double scale0,
+                             hipStream_t s);
+hipError_t launch_dct3_pre(const double *x, int64_t ldx, int64_t r0, int64_t cnt, int64_t n,
+                           int64_t N, const cd *wk, double a0, cd *spec, hipStream_t s);
+hipError_t launch_dct3_store(const cd *spec, int64_t N, int64_t r0, int64_t cnt, double *out,
+                             int64_t ldo, double scale, hipStream_t s);
+hipError_t launch_dct_n1(const double *x, int64_t ldx, double *out, int64_t ldo, int64_t rows,
+                         double c, hipStream_t s);
 // Recursive filtering of real rows by S second-order sections (sosfilt.hip).
 // A launch filters the virtual row of io.n samples of every channel from the
 // states zi (channels x S x 2; NULL: zeros) and leaves the states after the

@@ -239,6 +239,44 @@ def hilbert_batch(x, N=None, kind: str = "analytic", out=None, work=None, stream
     return out
 
 
+def dct_batch(x, n=None, type=2, norm=None, inverse: bool = False, out=None, work=None,
+              stream=None):
+    """fft.DCTBatch (inverse: fft.IDCTBatch) on a float64 CUDA tensor (rows,
+    nx; unit inner stride, any row stride): every row cut or zero-padded to n
+    samples (None: nx) and its cosine transform of type 2 or 3 under scipy's
+    norm into out (rows, n; float64, unit inner stride, any row stride). out
+    may be x itself (n <= nx; the same row stride), nothing else that overlaps
+    it, and is allocated only when not given. work: scratch (any dtype) of
+    gdsp_dct_work_doubles(rows, n) float64 for the composed form; the fused
+    form (fft.dct_fused(n)) takes none, and with work given a call neither
+    allocates nor synchronises."""
+    from .fft import dct_kind, dct_length
+    torch = _torch()
+    assert x.is_cuda and x.dtype == torch.float64 and x.dim() == 2
+    t, k = dct_kind(type, norm, inverse, "dct_batch")
+    nfft = dct_length(n, "dct_batch")  # ValueError below 1, as scipy
+    rows, nx = x.shape
+    nfft = nx if nfft is None else nfft
+    if out is None:
+        out = torch.empty((rows, max(nfft, 0)), dtype=torch.float64, device=x.device)
+    assert out.is_cuda and out.dtype == torch.float64 and out.device == x.device
+    assert tuple(out.shape) == (rows, max(nfft, 0))
+    assert nx == 0 or x.stride(1) == 1, "rows must have unit inner stride"
+    assert nfft <= 0 or out.stride(1) == 1, "rows must have unit inner stride"
+    ldx = x.stride(0) if rows > 1 else nx
+    ldo = out.stride(0) if rows > 1 else nfft
+    if work is not None:
+        assert work.is_cuda and work.device == x.device and work.is_contiguous()
+        need = int(lib().gdsp_dct_work_doubles(rows, nfft)) * 8
+        assert work.numel() * work.element_size() >= need and work.data_ptr() % 16 == 0
+    with torch.cuda.device(x.device):
+        wp = _ptr(work) if work is not None else ctypes.c_void_p()
+        check(lib().gdsp_dct_batch_device(_ptr(x), ldx, rows, nx, nfft, t, k, _ptr(out), ldo, wp,
+                                          _stream_ptr(stream, x.device)),
+              "dct_batch_device")
+    return out
+
+
 class CztPlan:
     """A chirp-z plan on the current device (gdsp_czt_plan_create): X[k] =
     sum_j x[j] z_k^-j on the m points z_k = a_abs exp(2 pi i (a_turns + k

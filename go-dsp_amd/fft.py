@@ -252,6 +252,86 @@ def Envelope(x, N=None) -> np.ndarray:
     return EnvelopeBatch(np.asarray(x, dtype=np.float64).reshape(1, -1), N)[0]
 
 
+def dct_fused(N: int) -> bool:
+    """Whether DCTBatch / IDCTBatch run transform length N on the fused
+    cosine-transform kernel under the current algorithm flags (gdsp_dct_fused;
+    host arithmetic)."""
+    return bool(lib().gdsp_dct_fused(int(N)))
+
+
+_DCT_NORMS = {None: _lib.GDSP_DCT_BACKWARD, "backward": _lib.GDSP_DCT_BACKWARD,
+              "ortho": _lib.GDSP_DCT_ORTHO, "forward": _lib.GDSP_DCT_FORWARD}
+_DCT_OPPOSITE = {_lib.GDSP_DCT_BACKWARD: _lib.GDSP_DCT_FORWARD,
+                 _lib.GDSP_DCT_ORTHO: _lib.GDSP_DCT_ORTHO,
+                 _lib.GDSP_DCT_FORWARD: _lib.GDSP_DCT_BACKWARD}
+
+
+def dct_kind(type, norm, inverse: bool = False, what: str = "DCT"):
+    """(type, norm) of the C ABI for scipy's arguments. The inverse of (2, norm)
+    is (3, the opposite norm) and the other way round; opposite swaps backward
+    and forward and keeps ortho."""
+    if isinstance(type, bool) or type not in (2, 3):
+        raise ValueError(f"{what}: type must be 2 or 3, not {type!r}")
+    if not (norm is None or isinstance(norm, str)) or norm not in _DCT_NORMS:
+        raise ValueError(f"{what}: norm must be None, 'backward', 'ortho' or 'forward', "
+                         f"not {norm!r}")
+    t, k = int(type), _DCT_NORMS[norm]
+    return (5 - t, _DCT_OPPOSITE[k]) if inverse else (t, k)
+
+
+def dct_length(n, what: str = "DCT"):
+    """scipy's n= as a transform length: None (the row length) or an integer of
+    at least 1. scipy.fft.dct raises ValueError below 1; so does this, before
+    anything is allocated: the C ABI reads nfft = 0 as "the row length", which
+    an output of n = 0 columns would not hold."""
+    if n is None:
+        return None
+    if isinstance(n, bool) or int(n) != n or int(n) < 1:
+        raise ValueError(f"{what}: invalid number of data points ({n!r}) specified")
+    return int(n)
+
+
+def _dct(rows, type, n, norm, inverse: bool, what: str) -> np.ndarray:
+    t, k = dct_kind(type, norm, inverse, what)
+    nfft = dct_length(n, what)
+    x = _real_rows(rows, what)
+    r, nx = x.shape
+    nfft = nx if nfft is None else nfft
+    out = np.empty((r, nfft), np.float64)
+    check(lib().gdsp_dct_batch(_p(x), nx, r, nx, nfft, t, k, _p(out), nfft), what)
+    return out
+
+
+def DCTBatch(rows, type=2, n=None, norm=None) -> np.ndarray:
+    """Additive cosine transform of every row of the real (rows, nx) array (or
+    list of rows): scipy.fft.dct(rows, type, n=n, axis=1, norm=norm) for type
+    2 or 3 — each row cut or zero-padded to n samples (None: nx); float64
+    (rows, n)."""
+    return _dct(rows, type, n, norm, False, "DCTBatch")
+
+
+def IDCTBatch(rows, type=2, n=None, norm=None) -> np.ndarray:
+    """scipy.fft.idct(rows, type, n=n, axis=1, norm=norm): the DCT of the other
+    type under the opposite norm (dct_kind)."""
+    return _dct(rows, type, n, norm, True, "IDCTBatch")
+
+
+def DCT(x, type=2, n=None, norm=None) -> np.ndarray:
+    """scipy.fft.dct(x, type, n=n, norm=norm) of the real signal x (DCTBatch
+    of one row)."""
+    if np.iscomplexobj(x):
+        raise TypeError("DCT: complex input is not supported")
+    return _dct(np.asarray(x, dtype=np.float64).reshape(1, -1), type, n, norm, False, "DCT")[0]
+
+
+def IDCT(x, type=2, n=None, norm=None) -> np.ndarray:
+    """scipy.fft.idct(x, type, n=n, norm=norm) of the real signal x (IDCTBatch
+    of one row)."""
+    if np.iscomplexobj(x):
+        raise TypeError("IDCT: complex input is not supported")
+    return _dct(np.asarray(x, dtype=np.float64).reshape(1, -1), type, n, norm, True, "IDCT")[0]
+
+
 def _sos(sos, what: str) -> np.ndarray:
     """Sections as a contiguous (S, 6) float64 array."""
     if np.iscomplexobj(sos):
@@ -710,6 +790,7 @@ ALGO_NO_FUSED_UPFIRDN = 8192
 ALGO_NO_FUSED_HILBERT = 32768  # 16384 is not a flag
 ALGO_NO_FUSED_SOSFILT = 65536
 ALGO_NO_FUSED_CZT = 262144  # 131072 is not a flag
+ALGO_NO_FUSED_DCT = 1 << 21  # 1 << 19 and 1 << 20 are not flags
 
 
 def SetAlgorithm(flags: int = ALGO_DEFAULT) -> None:

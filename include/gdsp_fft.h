@@ -146,7 +146,15 @@ enum {
    * kernel) also for the convolution lengths the fused chirp-z kernel serves;
    * gdsp_czt_fused then reports 0. Read when the call is made. The bit 131072
    * is not used, like 2048 and 16384: all three stay unknown bits. */
-  GDSP_ALGO_NO_FUSED_CZT = 262144
+  GDSP_ALGO_NO_FUSED_CZT = 262144,
+  /* gdsp_dct_batch / gdsp_dct_batch_device on the composed form (type II: a
+   * permute-and-pad kernel, the plan's real-row transform, a twiddle-and-store
+   * kernel; type III: a kernel that writes the rows of conj W, the plan's
+   * transform, an un-permute store) also for the powers of 2 the fused
+   * cosine-transform kernel serves; gdsp_dct_fused then reports 0. Read when
+   * the call is made. The bits 1 << 19 and 1 << 20 are not used, like 2048,
+   * 16384 and 131072: all five stay unknown bits. */
+  GDSP_ALGO_NO_FUSED_DCT = 2097152
 };
 /* Unknown bits → GDSP_ERR_INVALID (the selection is left unchanged). */
 int gdsp_set_algorithm(unsigned flags);
@@ -235,7 +243,19 @@ unsigned gdsp_get_algorithm(void);
  *                             row non-finite, in both parts, and changes no bit
  *                             elsewhere; rows times 2^k give outputs times 2^k
  *                             (the inverse's 1 / F is a power of 2, folded into
- *                             the chirp's spectrum) (tests/test_czt_gpu.py) */
+ *                             the chirp's spectrum) (tests/test_czt_gpu.py)
+ *      DCT                   (gdsp_dct_batch, gdsp_dct_batch_device, both types,
+ *                             every norm, both forms) a row depends on itself
+ *                             alone, bit for bit, whatever its neighbours hold
+ *                             and however a job is cut into calls, ranges or
+ *                             chunks. A row of zeros gives exact zeros; rows
+ *                             times 2^k give outputs times 2^k for every norm
+ *                             (each norm is one multiplication by a constant
+ *                             after the transform; ortho's type III one more on
+ *                             x[0] before it). A NaN or Inf in a row makes
+ *                             every output of that row non-finite and changes
+ *                             no bit of another row. Stale out and work
+ *                             contents change nothing (tests/test_dct_gpu.py) */
 
 /* ---- fft package: host pointers, synchronous ----------------------------- */
 
@@ -514,6 +534,55 @@ int gdsp_czt_fused(int64_t n, int64_t m);
 int gdsp_czt_batch(const void *x, int64_t ldx, int is_real, int64_t rows, int64_t n, int64_t m,
                    double a_abs, double a_turns, double step_turns, int64_t step_div, double *out,
                    int64_t ldo);
+
+/* Additive cosine transforms of real rows (no reference equivalent;
+ * scipy.fft.dct(x, type, n=N, norm=...), types II and III): for `rows` rows of
+ * n float64, row r at x + r*ldx, and a transform length N (nfft; 0: n), row r
+ * is cut to N samples or padded with zeros to N, and N float64 go to out +
+ * r*ldo:
+ *   type 2  y[k] = 2 sum_{j<N} x[j] cos(pi k (2j+1) / (2N))
+ *   type 3  y[j] = x[0] + 2 sum_{1<=k<N} x[k] cos(pi k (2j+1) / (2N))
+ *   GDSP_DCT_BACKWARD  as written
+ *   GDSP_DCT_FORWARD   both types times 1 / (2N)
+ *   GDSP_DCT_ORTHO     type 2: y[0] sqrt(1 / (4N)), y[k >= 1] sqrt(1 / (2N));
+ *                      type 3: the backward type 3 of (sqrt(2) x[0], x[1], ...)
+ *                      times sqrt(1 / (2N))
+ * The inverse of (type 2, norm) is (type 3, the opposite norm) and the other
+ * way round, where opposite swaps backward and forward and keeps ortho: the
+ * callers' mapping, not another entry. One N-point transform per row (Makhoul):
+ * v[j] = x[2j], v[N-1-j] = x[2j+1], w_k = exp(-i pi k / (2N)); type 2 is 2
+ * Re(w_k FFT_N(v)[k]); type 3 the transform of (x[k] + i x[N-k]) w_k, its real
+ * parts un-permuted. Where gdsp_dct_fused(N), one kernel per call: load,
+ * permutation, transform, w_k, scale and store in one workgroup; otherwise the
+ * composed form around the plan's transform in chunks of at most 2^24 samples
+ * (N = 1 needs no transform). Longer host jobs are cut into ranges of rows of
+ * at most 2^24 samples; a row's bits do not depend on the range or chunk it
+ * falls in.
+ * In this order, before any device call: a negative size, a type outside {2,
+ * 3}, a norm outside 0..2, or, with rows > 1, ldx < min(n, N) or ldo < N ->
+ * GDSP_ERR_INVALID; rows == 0 -> GDSP_OK, nothing done; n == 0 or N == 0 ->
+ * GDSP_ERR_EMPTY; a NULL pointer -> GDSP_ERR_INVALID; N > 2^20 ->
+ * GDSP_ERR_UNSUPPORTED. Runs on the current device. */
+enum { GDSP_DCT_BACKWARD = 0, GDSP_DCT_ORTHO = 1, GDSP_DCT_FORWARD = 2 };
+int gdsp_dct_batch(const double *x, int64_t ldx, int64_t rows, int64_t n, int64_t nfft,
+                   int type, int norm, double *out, int64_t ldo);
+/* 1 where the fused cosine-transform kernel serves transform length nfft under
+ * the current flags (a power of 2 from 256 to 16384, without
+ * GDSP_ALGO_NO_FUSED_DCT), 0 where the composed form runs or nothing does.
+ * Host arithmetic only, no GPU needed. */
+int gdsp_dct_fused(int64_t nfft);
+/* float64 of d_work for `rows` rows under the current flags: 0 where
+ * gdsp_dct_fused(nfft), for nfft <= 1, nfft > 2^20 or rows <= 0; otherwise
+ * 3 * R * nfft, R = min(rows, max(1, 2^24 div nfft)): R rows of nfft
+ * complex128, then R rows of nfft float64. Host arithmetic. */
+int64_t gdsp_dct_work_doubles(int64_t rows, int64_t nfft);
+/* The table w_k = exp(-i pi k / (2 nfft)), k < nfft, as the kernels read it:
+ * re_im[2k] = cos(pi k / (2 nfft)), re_im[2k+1] = -sin(pi k / (2 nfft)),
+ * evaluated in long double on angles of at most pi/4 (past nfft/2 through the
+ * complement) and rounded once. Host only. nfft < 0 -> GDSP_ERR_INVALID; 0 ->
+ * GDSP_ERR_EMPTY; a NULL pointer -> GDSP_ERR_INVALID; nfft > 2^20 ->
+ * GDSP_ERR_UNSUPPORTED. */
+int gdsp_dct_twiddles(int64_t nfft, double *re_im);
 
 /* Additive batched entry point (no reference equivalent): the
  * same transform as fft.FFT / fft.IFFT applied to `batch` contiguous rows of n
@@ -808,6 +877,7 @@ int gdsp_multi_stats(int64_t *batch_calls, int64_t *pwelch_calls, int64_t *rccl_
  * of gdsp_hilbert_batch and the row chunks of its composed form, the time
  * chunks of gdsp_sosfilt_batch and of both passes of gdsp_sosfiltfilt_batch,
  * the row ranges of gdsp_czt_batch and the row chunks of its composed form,
+ * the row ranges of gdsp_dct_batch and the row chunks of its composed form,
  * and the 65535-row pieces of gdsp_fft_axis_device / gdsp_fftn_device and of the
  * multi-pass, four-step and chirp-z executors).
  * multi_unit_launches: launches of a Pwelch, batched-Pwelch, Cpsd, STFT or ISTFT kernel
@@ -975,6 +1045,20 @@ int gdsp_sosfiltfilt_batch_device(const void *d_x, int64_t ldx, const double *so
 int gdsp_hilbert_batch_device(const void *d_x, int64_t ldx, int64_t rows, int64_t n,
                               int64_t nfft, int kind, void *d_out, int64_t ldo,
                               void *d_work, void *stream);
+
+/* gdsp_dct_batch on device buffers (no reference equivalent), stream-ordered:
+ * d_x rows of n float64 at stride ldx, d_out rows of N float64 at stride ldo.
+ * d_out may be exactly d_x (the same pointer, ldo == ldx, N <= n): a workgroup,
+ * or the gather of a chunk, has read a whole row before any of it is stored.
+ * Every other overlap of the address ranges -> GDSP_ERR_INVALID, decided after
+ * gdsp_dct_batch's own checks. d_work (may be NULL: the library's workspace
+ * pool): gdsp_dct_work_doubles(rows, N) float64, 16-byte aligned. With d_work
+ * given, or where gdsp_dct_fused(N), a call neither allocates nor synchronises
+ * once the plan and the w_k table of N exist on the device (the first call for
+ * an N builds them). */
+int gdsp_dct_batch_device(const void *d_x, int64_t ldx, int64_t rows, int64_t n, int64_t nfft,
+                          int type, int norm, void *d_out, int64_t ldo, void *d_work,
+                          void *stream);
 
 /* The chirp-z transform's plan (gdsp_czt_batch's parameters, no reference
  * equivalent): the device tables A, FFT_F(v) / F (computed from the float64 v
